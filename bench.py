@@ -19,14 +19,21 @@ itself (python -m torch.distributed.run, one process per GPU, rendezvous on 127.
 before anything touches the GPU, and exits with their return code; under torchrun it is a
 rank.  Every rank checks that the world size equals --gpus.
 
-Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, plus
+Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, ms_per_step (wall time of
+one timed step) and the workload.  A plain run does only what that line needs: set up, warm up,
+time --steps steps.  --full adds, after the timed steps,
+  checks       -- structural parity gate on every segment table of the last step
+  upload       -- value_incl_upload, upload_alloc_s, runtime_init_s (weak mode)
   roofline     -- the kernel (forward pass with the decoding fused in): algorithmic HBM bytes
                   (24 B per (bin,penalty) + 20 B per stored piece; decoding: per
                   segment 12 B written, 8 B + 28 B per piece of the function read) / HIP-event
                   kernel time (events on the stream the kernel runs on), against 8 TB/s
   cpu_baseline -- the CPU oracle (libm build, disk-backed store like the reference) timed on
                   a bounded sample of the same workload on this host: one core, and all cores
-                  with a process pool (N=1 only).
+                  with a process pool (N=1 only; not with --no-cpu).
+
+--dump-outputs DIR writes the segment tables the last timed step returned as float64 .npy files
+(dump_outputs); the inputs are seeded, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -60,7 +67,40 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-bins-all", type=int, default=1000000,
                     help="CPU baseline, all cores: first this many bins x every penalty")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gate, upload timing, roofline and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last step's segment tables to DIR/<name>.npy")
     return ap.parse_args(argv)
+
+
+# --dump-outputs: at most this many table rows (x 3 float64 files = 48 MiB); a longer
+# concatenation is written as a seeded sample of its rows
+DUMP_MAX_ROWS = 2 ** 21
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, tables, summary=None, max_rows=DUMP_MAX_ROWS):
+    """tables: list of (seg_start, seg_mean) in problem order, as the step returned them.
+    Writes float64 arrays: seg_rows (rows per table), seg_row_index (which rows of the
+    concatenated tables follow: all of them, or a sorted seeded sample of max_rows when there
+    are more), seg_start and seg_mean (those rows), and summary when given."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.array([len(s) for s, _ in tables], dtype=np.float64)
+    start = np.concatenate([np.asarray(s, dtype=np.float64) for s, _ in tables] or [np.zeros(0)])
+    mean = np.concatenate([np.asarray(m, dtype=np.float64) for _, m in tables] or [np.zeros(0)])
+    if len(start) > max_rows:
+        index = np.sort(np.random.default_rng(DUMP_SEED).choice(len(start), max_rows,
+                                                                replace=False))
+    else:
+        index = np.arange(len(start))
+    arrays = {"seg_rows": rows, "seg_row_index": index.astype(np.float64),
+              "seg_start": start[index], "seg_mean": mean[index]}
+    if summary is not None:
+        arrays["summary"] = np.asarray(summary, dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_model_name():
@@ -179,6 +219,41 @@ def grid_contig_lengths(n_contigs, scale):
     return [max(64, int(round(scale * 10.0 ** (5.0 + 2.0 * x)))) for x in u]
 
 
+def headline(args, world, units_per_step, elapsed, lengths):
+    """The fields of the result line that a plain run prints (lengths: grid mode's contigs)."""
+    if args.mode == "weak":
+        workload = ("%d-bin synthetic Poisson coverage x %d-penalty grid per GPU "
+                    "(BASELINE.json configs[1])" % (args.bins, args.penalties))
+        cfg = {"workload": workload, "bins": args.bins, "penalties": args.penalties,
+               "penalty_grid": "10^seq(-1,5), 15 significant digits", "seed": "1+rank",
+               "sharding": "independent (contig x penalty) problems per rank; RCCL gather "
+                           "of segment tables to rank 0"}
+    else:
+        workload = ("%d synthetic contigs of %d..%d bins (log-uniform) x %d penalties "
+                    "dealt longest-first to %d rank(s) (BASELINE.json configs[3])"
+                    % (len(lengths), min(lengths), max(lengths), args.penalties, world))
+        cfg = {"workload": workload, "contigs": len(lengths), "total_bins": sum(lengths),
+               "penalties": args.penalties, "grid_scale": args.grid_scale,
+               "sharding": "LPT dealing of (contig x penalty) problems; one RCCL gather of "
+                           "segment tables + summaries to rank 0; upload inside the timed "
+                           "region"}
+    return {
+        "metric": "coverage bins/sec across 64-penalty grid",
+        "value": units_per_step * args.steps / elapsed,
+        "unit": "bins/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak" if args.mode == "weak" else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": cfg,
+    }
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -253,7 +328,15 @@ def main():
         if dist is not None:
             dist.barrier()
 
+    def finish():
+        if args.mode == "weak":
+            pset.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
     extra = {}
+    lengths = None
     if args.mode == "weak":
         # every rank: its own contig (seed 1 + rank), the same penalty grid
         cs, ce, cnt = synthetic.poisson_coverage(args.bins, seed=1 + rank)
@@ -263,10 +346,11 @@ def main():
         # process, whatever is solved afterwards): a one-bin set pays it here, so that create_s
         # is what SURVEY.md 8(d) counts -- upload and allocation of THIS set
         # (profiles/r04/create_timing.log: 0.45 s for the first set of a process, 0.02 s for
-        # the second and third).
-        t_c = time.time()
-        ProblemSet([(cnt[:2], weight[:2])], [(0, 1.0)], device=device).close()
-        runtime_init_s = time.time() - t_c
+        # the second and third).  --full only: a plain run reports no upload figures.
+        if args.full:
+            t_c = time.time()
+            ProblemSet([(cnt[:2], weight[:2])], [(0, 1.0)], device=device).close()
+            runtime_init_s = time.time() - t_c
         t_c = time.time()
         pset = ProblemSet([(cnt, weight)], problems, device=device)
         create_s = time.time() - t_c
@@ -311,6 +395,21 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if on_gpu else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if rank == 0 and args.dump_outputs:
+        if args.mode == "weak":
+            # every rank's tables, rank by rank, each in penalty order
+            dump_outputs(args.dump_outputs, [t for tables, _ in gathered for t in tables])
+        else:
+            keys = sorted(gathered)  # (contig, penalty index)
+            dump_outputs(args.dump_outputs,
+                         [(gathered[k]["seg_start"], gathered[k]["seg_mean"]) for k in keys],
+                         np.array([gathered[k]["summary"] for k in keys], dtype=np.float64))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, units_per_step, elapsed, lengths)))
+        finish()
+        return
 
     # parity gate on what was just computed: structural checks that hold for every solution
     if args.mode == "weak":
@@ -367,7 +466,6 @@ def main():
                                          if k in stats}}
 
     if rank == 0:
-        units = units_per_step * args.steps
         # HBM traffic of one forward launch from the PMC counters (collected separately with
         # rocprofv3 --pmc by tools/collect_profiles.sh); only valid for that workload
         traffic = None
@@ -392,57 +490,27 @@ def main():
         n_prob_rank0 = len(problems) if args.mode == "weak" else stats.get("problems", 0)
         wave_slots_used = n_prob_rank0 * (4 if extra.get("kernel_build") == "lat" else 2)
         wave_slots_used = min(wave_slots_used, 8192)
-        if args.mode == "weak":
-            workload = ("%d-bin synthetic Poisson coverage x %d-penalty grid per GPU "
-                        "(BASELINE.json configs[1])" % (args.bins, args.penalties))
-            cfg = {"workload": workload, "bins": args.bins, "penalties": args.penalties,
-                   "penalty_grid": "10^seq(-1,5), 15 significant digits", "seed": "1+rank",
-                   "sharding": "independent (contig x penalty) problems per rank; RCCL gather "
-                               "of segment tables to rank 0"}
-        else:
-            workload = ("%d synthetic contigs of %d..%d bins (log-uniform) x %d penalties "
-                        "dealt longest-first to %d rank(s) (BASELINE.json configs[3])"
-                        % (len(lengths), min(lengths), max(lengths), args.penalties, world))
-            cfg = {"workload": workload, "contigs": len(lengths), "total_bins": sum(lengths),
-                   "penalties": args.penalties, "grid_scale": args.grid_scale,
-                   "sharding": "LPT dealing of (contig x penalty) problems; one RCCL gather of "
-                               "segment tables + summaries to rank 0; upload inside the timed "
-                               "region"}
-        out = {
-            "metric": "coverage bins/sec across 64-penalty grid",
-            "value": units / elapsed,
-            "unit": "bins/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak" if args.mode == "weak" else "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": cfg,
-            "roofline": {
-                "bound": "hbm", "kernel": "fpop_forward_kernel",
-                "achieved": alg_bytes / fwd_s / 1e9 if fwd_s > 0 else None,
-                "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": alg_bytes / fwd_s / 1e9 / HBM_PEAK_GBS if fwd_s > 0 else None,
-                "traffic": traffic,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "kernel_ms": float(np.mean(fwd)),  # forward pass + decoding, one launch
-                "dp_steps_per_s_per_problem":
-                    (args.bins / fwd_s if args.mode == "weak" and fwd_s > 0 else None),
-                # what actually bounds the kernel: the length of one
-                # wave's dependent instruction chain per data point, on the slowest problem of
-                # the launch (the kernel ends when it does), and how little of the chip a
-                # 64-problem grid can occupy
-                "cycles_per_step_slowest_problem":
-                    (fwd_s * clock_hz / args.bins if args.mode == "weak" and clock_hz else None),
-                "shader_clock_mhz": clock_hz / 1e6 if clock_hz else None,
-                "wave_slots_used": wave_slots_used,
-                "wave_slots": 8192,
-                "mean_intervals": total_pieces / (2.0 * bins_launch * (world if args.mode == "grid" else 1)),
-            },
+        out = headline(args, world, units_per_step, elapsed, lengths)
+        out["roofline"] = {
+            "bound": "hbm", "kernel": "fpop_forward_kernel",
+            "achieved": alg_bytes / fwd_s / 1e9 if fwd_s > 0 else None,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": alg_bytes / fwd_s / 1e9 / HBM_PEAK_GBS if fwd_s > 0 else None,
+            "traffic": traffic,
+            "algorithmic_bytes_per_launch": alg_bytes,
+            "kernel_ms": float(np.mean(fwd)),  # forward pass + decoding, one launch
+            "dp_steps_per_s_per_problem":
+                (args.bins / fwd_s if args.mode == "weak" and fwd_s > 0 else None),
+            # what actually bounds the kernel: the length of one
+            # wave's dependent instruction chain per data point, on the slowest problem of
+            # the launch (the kernel ends when it does), and how little of the chip a
+            # 64-problem grid can occupy
+            "cycles_per_step_slowest_problem":
+                (fwd_s * clock_hz / args.bins if args.mode == "weak" and clock_hz else None),
+            "shader_clock_mhz": clock_hz / 1e6 if clock_hz else None,
+            "wave_slots_used": wave_slots_used,
+            "wave_slots": 8192,
+            "mean_intervals": total_pieces / (2.0 * bins_launch * (world if args.mode == "grid" else 1)),
         }
         # What bounds a data point from below (tools/chain_floor.py, profiles/r04/chain_floor.json:
         # the dependent chain of the slower chain wave priced with this repository's own probe
@@ -480,11 +548,7 @@ def main():
             out["gpu_over_cpu_core_at_length"] = \
                 out["value"] / out["cpu_baseline"]["one_core_at_length"]["value"]
         print(json.dumps(out))
-    if args.mode == "weak":
-        pset.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

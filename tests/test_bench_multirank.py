@@ -30,7 +30,7 @@ def _worker(rank, world, port, out_q, extra_args=()):
         os.path.join(ROOT, "tests", "emu", "_build", "libpeaksegdisk_emu.so")))
     import bench
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--bins", "400",
-                "--penalties", "4", "--no-cpu"] + list(extra_args)
+                "--penalties", "4", "--no-cpu", "--full"] + list(extra_args)
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()

@@ -6,6 +6,8 @@ Poisson loss within 1e-6 relative (BASELINE.json north_star)."""
 import ctypes
 import os
 import shutil
+import tempfile
+from unittest import mock
 
 import numpy as np
 import pytest
@@ -195,10 +197,14 @@ def test_synthetic_grid_vs_oracle(psd, oracle_det, oracle_libm, tmp_path, n_bins
 def test_python_entry_points(psd, tmp_path, with_search=True):
     """PeakSegFPOP_vec / _df / _dir / sequentialSearch_dir through the HIP library, with the
     reference tests' expectations (test-CRAN-PeakSegFPOP_vec.R, test-TRAVIS-sequentialSearch.R)."""
-    fit_inf = psd.PeakSegFPOP_vec(np.array([1, 3, 0, 4, 2], dtype=np.int32), float("inf"))
-    assert len(fit_inf.segments) == 1
-    fit0 = psd.PeakSegFPOP_vec(np.array([1, 3, 0, 4, 2], dtype=np.int32), 0)
-    assert len(fit0.segments) == 5
+    # PeakSegFPOP_vec writes its problem directory under tempfile.gettempdir() (R's tempdir()):
+    # this test's own directory, not one that another user's run may own
+    with mock.patch.object(tempfile, "tempdir", str(tmp_path)):
+        fit_inf = psd.PeakSegFPOP_vec(np.array([1, 3, 0, 4, 2], dtype=np.int32), float("inf"))
+        assert len(fit_inf.segments) == 1
+        fit0 = psd.PeakSegFPOP_vec(np.array([1, 3, 0, 4, 2], dtype=np.int32), 0)
+        assert len(fit0.segments) == 5
+    assert (tmp_path / "chrUnknown-0-5" / "coverage.bedGraph").exists()
     d = tmp_path / "chr11-60000-580000"
     d.mkdir()
     shutil.copy(os.path.join(GOLDEN, "Mono27ac.bedGraph"), str(d / "coverage.bedGraph"))

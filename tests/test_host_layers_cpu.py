@@ -217,10 +217,10 @@ def test_bench_refuses_a_world_that_is_not_gpus():
 
 
 def test_bench_single_rank_line_on_emulator():
-    """N = 1 through the emulator: the JSON line carries roofline, cpu_baseline with both
-    legs (one core, all cores) and the upload-inclusive rate."""
+    """N = 1 through the emulator, --full: the JSON line carries roofline, cpu_baseline with
+    both legs (one core, all cores) and the upload-inclusive rate."""
     env = {"PSD_BENCH_BACKEND": "gloo", "PSD_BENCH_TEST_LIB": _emu_lib()}
-    p = _run_bench(["--steps", "1", "--warmup", "0", "--bins", "400", "--penalties", "3",
+    p = _run_bench(["--full", "--steps", "1", "--warmup", "0", "--bins", "400", "--penalties", "3",
                     "--cpu-bins", "200", "--cpu-bins-all", "400"], env)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
@@ -230,6 +230,74 @@ def test_bench_single_rank_line_on_emulator():
     assert cb["all_cores"]["cores"] >= 1 and cb["all_cores"]["value"] > 0 and cb["cpu_model"]
     assert "all 3 penalties" in cb["sample"]
     assert d["value_incl_upload"] > 0 and d["value_incl_upload"] <= d["value"] * 1.0001
+
+
+def _dumped(out_dir):
+    return {name[:-4]: np.load(os.path.join(out_dir, name)) for name in os.listdir(out_dir)}
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline fields only (no CPU baseline, no roofline), times
+    exactly --steps steps, and --dump-outputs writes the last step's segment tables as float64
+    .npy files that are the same from run to run (seeded inputs)."""
+    env = {"PSD_BENCH_BACKEND": "gloo", "PSD_BENCH_TEST_LIB": _emu_lib()}
+    dumps = []
+    for k in range(2):
+        out_dir = str(tmp_path / ("run%d" % k))
+        p = _run_bench(["--steps", "3", "--warmup", "1", "--bins", "400", "--penalties", "3",
+                        "--dump-outputs", out_dir], env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        d = json.loads(lines[0])
+        assert d["metric"] == "coverage bins/sec across 64-penalty grid" and d["unit"] == "bins/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == 3
+        assert abs(d["value"] - 400 * 3 * 3 / (d["ms_per_step"] * 3 / 1e3)) < 1e-6 * d["value"]
+        assert "cpu_baseline" not in d and "roofline" not in d and "value_incl_upload" not in d
+        dumps.append(_dumped(out_dir))
+    a, b = dumps
+    assert sorted(a) == ["seg_mean", "seg_row_index", "seg_rows", "seg_start"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    for name in a:
+        assert np.array_equal(a[name].view(np.uint64), b[name].view(np.uint64)), name
+    rows = a["seg_rows"].astype(int)
+    assert len(rows) == 3 and rows.sum() == len(a["seg_start"]) == len(a["seg_mean"])
+    assert np.array_equal(a["seg_row_index"], np.arange(rows.sum()))
+    ends = np.cumsum(rows) - 1  # the reference's order: last segment first, it starts at -1
+    assert (a["seg_start"][ends] == -1).all() and (rows % 2 == 1).all()
+
+
+def test_bench_grid_mode_dumps_summaries(tmp_path):
+    """--mode grid: the step returns a summary row per (contig, penalty) with the tables; the
+    dump holds both, in (contig, penalty) order."""
+    env = {"PSD_BENCH_BACKEND": "gloo", "PSD_BENCH_TEST_LIB": _emu_lib()}
+    out_dir = str(tmp_path / "grid")
+    p = _run_bench(["--mode", "grid", "--steps", "1", "--warmup", "0", "--grid-contigs", "3",
+                    "--grid-scale", "0.002", "--penalties", "2", "--dump-outputs", out_dir], env)
+    assert p.returncode == 0, p.stderr[-2000:]
+    a = _dumped(out_dir)
+    assert a["summary"].shape == (6, 5) and a["summary"].dtype == np.float64
+    assert np.array_equal(a["summary"][:, 0], a["seg_rows"])  # n_segments per problem
+    assert a["seg_rows"].sum() == len(a["seg_start"])
+
+
+def test_dump_outputs_samples_long_tables_with_a_fixed_seed(tmp_path):
+    """Beyond max_rows the concatenated tables are written as the same seeded sample of rows
+    every time; the index says which rows they are."""
+    import bench
+    rng = np.random.default_rng(5)
+    tables = [(np.arange(n, dtype=np.int32)[::-1] - 1, rng.standard_normal(n)) for n in (7, 0, 31)]
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), tables, max_rows=10)
+    a, b = _dumped(str(tmp_path / "0")), _dumped(str(tmp_path / "1"))
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    idx = a["seg_row_index"].astype(int)
+    assert len(idx) == 10 and (np.diff(idx) > 0).all() and idx[-1] < 38
+    start = np.concatenate([s for s, _ in tables]).astype(np.float64)
+    mean = np.concatenate([m for _, m in tables])
+    assert np.array_equal(a["seg_start"], start[idx]) and np.array_equal(a["seg_mean"], mean[idx])
+    assert list(a["seg_rows"]) == [7, 0, 31]
 
 
 def test_write_failures_on_the_host_only_branch(tmp_path):

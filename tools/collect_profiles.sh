@@ -10,11 +10,11 @@ OUT=$REPO/gpurun_out/prof
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 echo "== bench (default: 1e6 bins x 64 penalties)"
-python3 "$REPO/bench.py" > "$OUT/bench_1e6x64_full.json.log" 2>&1 || exit 1
+python3 "$REPO/bench.py" --full > "$OUT/bench_1e6x64_full.json.log" 2>&1 || exit 1
 grep metric "$OUT/bench_1e6x64_full.json.log" | cut -c1-400
 echo "== rocprofv3 --kernel-trace --stats (100k bins)"
 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o bench100k -- \
-  python3 "$REPO/bench.py" --bins 100000 --steps 3 --warmup 1 --no-cpu \
+  python3 "$REPO/bench.py" --full --bins 100000 --steps 3 --warmup 1 --no-cpu \
   > "$OUT/bench100k_under_rocprofv3.json.log" 2>&1 || exit 1
 grep metric "$OUT/bench100k_under_rocprofv3.json.log" | cut -c1-300
 for c in FETCH_SIZE WRITE_SIZE; do
