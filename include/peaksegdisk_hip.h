@@ -37,8 +37,20 @@ extern "C" {
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
  *                               per GPU sets it from its rank
- * PEAKSEG_HIP_MAX_BYTES         cap on the HBM one problem set may hold (suffix K/M/G/T); several
- *                               processes can then share one GPU (R's future workers)
+ * PEAKSEG_HIP_DEVICES=all|0,1,..  fan-out inside one process (takes precedence over
+ *                               PEAKSEG_HIP_DEVICE): PeakSegFPOP_disk_batch, PeakSegFPOP_dir_batch
+ *                               and PeakSegFPOP_sequential_search_batch deal their dynamic programs
+ *                               (the search batch: its directories) to one shard per listed device,
+ *                               longest predicted first, and solve each shard in a problem set of its
+ *                               own on a host thread of its own; an id listed twice gets two sets,
+ *                               one after the other.  PeakSegFPOP_disk and
+ *                               PeakSegFPOP_sequential_search use the first listed device.  A
+ *                               malformed list or an id that is not visible: the dynamic programs
+ *                               get ERROR_NO_HIP_DEVICE and no shard runs.  Unset or empty: one set
+ *                               on PEAKSEG_HIP_DEVICE's device, as without this knob
+ * PEAKSEG_HIP_MAX_BYTES         cap on the HBM one problem set (one shard's) may hold (suffix
+ *                               K/M/G/T); several processes can then share one GPU (R's future
+ *                               workers)
  * PEAKSEG_HIP_PIECES_PER_FUNCTION  arena estimate, pieces per stored cost function (default 7):
  *                               picks the arena's chunk and block sizes; the arena itself grows
  *                               block by block WHILE the kernel runs (a host thread maps ahead of
@@ -133,8 +145,25 @@ char *PeakSegFPOP_status_message(int status, const char *bedGraph, const char *p
                                  const char *db, char *buf, size_t buf_len);
 
 /* Where "problem: %d items on line %d" goes (the reference Rprintf()s it,
- * PeakSegFPOPLog.cpp:181).  NULL restores the default (stdout). */
+ * PeakSegFPOPLog.cpp:181).  NULL restores the default (stdout).  It is only ever called on the
+ * thread that called the entry point: the shard threads of PEAKSEG_HIP_DEVICES hand their lines
+ * to it, complete lines at a time, each directory's in their order. */
 void peakseg_hip_set_print(void (*print)(const char *text));
+
+/* What PEAKSEG_HIP_DEVICES did in the calling thread's last file-level call.  Returns S, the
+ * number of shards (the length of the device list), or 0 when that call did not fan out (knob
+ * unset or bad, a single-program entry point, or no dynamic program to deal).  Per shard, up to
+ * `capacity` of them: its device, the dynamic programs it solved and the seconds its problem
+ * sets existed (creation, solve, results, destruction; any array may be NULL).  After the join
+ * the calling thread's peakseg_hip_last_error() holds the first failing shard's text and
+ * peakseg_hip_last_warning() the first shard warning, in shard order. */
+int peakseg_hip_last_fanout(int capacity, int *shard_device, int *shard_programs,
+                            double *shard_seconds);
+/* For each of the first n entries of that call in input order (a problem; a directory for the
+ * search batch): the shard that solved it, or -1 where none did (a cache hit, a trivial model, a
+ * failure before the dynamic program, or no fan-out).  A duplicated entry reports the shard of
+ * its first copy.  Returns the number of entries of that call. */
+int peakseg_hip_last_fanout_entries(int n, int *shard_of);
 
 /* ---- device-resident problem sets (penalty x contig grids, benchmarking) ------------ */
 

@@ -144,6 +144,11 @@ def declare(lib):
     lib.peakseg_hip_problem_set_arena_stats.argtypes = [
         c.c_void_p, c.POINTER(c.c_ulonglong), c.POINTER(c.c_int), c.POINTER(c.c_int)]
     lib.peakseg_hip_problem_set_arena_stats.restype = c.c_int
+    lib.peakseg_hip_last_fanout.argtypes = [
+        c.c_int, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_double)]
+    lib.peakseg_hip_last_fanout.restype = c.c_int
+    lib.peakseg_hip_last_fanout_entries.argtypes = [c.c_int, c.POINTER(c.c_int)]
+    lib.peakseg_hip_last_fanout_entries.restype = c.c_int
     return lib
 
 
@@ -164,6 +169,7 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_park_stats", "peakseg_hip_problem_set_pack_tables",
     "peakseg_hip_problem_set_packed_download", "peakseg_hip_problem_set_cycles",
     "peakseg_hip_measured_rates", "peakseg_hip_spin_limit", "peakseg_hip_problem_set_max_spin",
+    "peakseg_hip_last_fanout", "peakseg_hip_last_fanout_entries",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -177,6 +183,23 @@ lib = declare(ctypes.CDLL(LIB_PATH))
 
 def last_error():
     return lib.peakseg_hip_last_error().decode(errors="replace")
+
+
+def last_fanout():
+    """What PEAKSEG_HIP_DEVICES did in this thread's last file-level call of the library:
+    {"device", "programs", "seconds"}: one item per shard (empty lists when the call did not fan
+    out); "shard_of": the shard of each entry of the call, in input order (-1: none)."""
+    import ctypes
+    n = lib.peakseg_hip_last_fanout(0, None, None, None)
+    device = (ctypes.c_int * max(n, 1))()
+    programs = (ctypes.c_int * max(n, 1))()
+    seconds = (ctypes.c_double * max(n, 1))()
+    n = lib.peakseg_hip_last_fanout(n, device, programs, seconds)
+    m = lib.peakseg_hip_last_fanout_entries(0, None)
+    shard_of = (ctypes.c_int * max(m, 1))()
+    lib.peakseg_hip_last_fanout_entries(m, shard_of)
+    return {"device": list(device[:n]), "programs": list(programs[:n]),
+            "seconds": list(seconds[:n]), "shard_of": list(shard_of[:m])}
 
 
 def status_message(status, bedgraph, penalty, db):

@@ -309,12 +309,39 @@ def PeakSegFPOP_vec(count_vec, pen_num):
 
 # ---- PeakSegFPOP_dir for a batch (additive) --------------------------
 
-def PeakSegFPOP_dir_batch(problem_dirs, penalty_params):
+class _devices_knob:
+    """PEAKSEG_HIP_DEVICES for the duration of one batch call: None leaves the environment as
+    it is; "all", a string such as "0,1" or a sequence of device ids sets it, and the previous
+    value (or its absence) is restored afterwards."""
+
+    def __init__(self, devices):
+        if devices is None or isinstance(devices, str):
+            self.value = devices
+        else:
+            self.value = ",".join("%d" % int(d) for d in devices)
+
+    def __enter__(self):
+        self.old = os.environ.get("PEAKSEG_HIP_DEVICES")
+        if self.value is not None:
+            os.environ["PEAKSEG_HIP_DEVICES"] = self.value
+
+    def __exit__(self, *exc):
+        if self.value is None:
+            return
+        if self.old is None:
+            del os.environ["PEAKSEG_HIP_DEVICES"]
+        else:
+            os.environ["PEAKSEG_HIP_DEVICES"] = self.old
+
+
+def PeakSegFPOP_dir_batch(problem_dirs, penalty_params, devices=None):
     """PeakSegFPOP_dir for many (problem.dir, penalty) pairs in one call of the native
     PeakSegFPOP_dir_batch: cached results are reused as PeakSegFPOP_dir would
     (R/PeakSegFPOP_dir.R:70-93), every other pair is solved in one device problem set (one
     parse and upload per distinct coverage.bedGraph) and gets its _timing.tsv.  Returns the
-    list of PeakSegFPOP_dir results, in order; `.cached` says which were reused."""
+    list of PeakSegFPOP_dir results, in order; `.cached` says which were reused.
+    devices: "all" or device ids -- one problem set per listed device, solved side by side
+    (PEAKSEG_HIP_DEVICES for this call; None: the environment decides)."""
     import ctypes
     if len(problem_dirs) != len(penalty_params):
         raise ValueError("problem_dirs and penalty_params must have the same length")
@@ -324,7 +351,8 @@ def PeakSegFPOP_dir_batch(problem_dirs, penalty_params):
     pstr = (ctypes.c_char_p * n)(*[p.encode() for p in pens])
     status = (ctypes.c_int * n)()
     cached = (ctypes.c_int * n)()
-    _native.lib.PeakSegFPOP_dir_batch(n, dirs, pstr, status, cached)
+    with _devices_knob(devices):
+        _native.lib.PeakSegFPOP_dir_batch(n, dirs, pstr, status, cached)
     out = []
     for i in range(n):
         bg = os.path.join(problem_dirs[i], "coverage.bedGraph")
@@ -389,12 +417,14 @@ def _search_result(problem_dir, rows, chosen):
     return out
 
 
-def sequentialSearch_dir_batch(problem_dirs, peaks_int, verbose=0):
+def sequentialSearch_dir_batch(problem_dirs, peaks_int, verbose=0, devices=None):
     """sequentialSearch_dir over several problem directories at once (additive): each directory
     gets the result sequentialSearch_dir(dir, peaks) gives, but the models the searches ask for
     in the same iteration are computed in one device launch
     (PeakSegFPOP_sequential_search_batch).  peaks_int: one target for all, or one per
-    directory.  Returns the list of results; a failed search raises for the first failure."""
+    directory.  devices: "all" or device ids -- the directories dealt to one shard per listed
+    device (PEAKSEG_HIP_DEVICES for this call; None: the environment decides).  Returns the
+    list of results; a failed search raises for the first failure."""
     import ctypes
     problem_dirs = list(problem_dirs)
     n = len(problem_dirs)
@@ -414,8 +444,9 @@ def sequentialSearch_dir_batch(problem_dirs, peaks_int, verbose=0):
     n_rows = (ctypes.c_int * n)()
     chosen = (ctypes.c_int * n)()
     status = (ctypes.c_int * n)()
-    _native.lib.PeakSegFPOP_sequential_search_batch(n, dirs, peaks, int(bool(verbose)), cap, rows,
-                                                    n_rows, chosen, status)
+    with _devices_knob(devices):
+        _native.lib.PeakSegFPOP_sequential_search_batch(n, dirs, peaks, int(bool(verbose)), cap,
+                                                        rows, n_rows, chosen, status)
     out = []
     for d in range(n):
         if status[d] == _native.ERROR_SEARCH_TOO_MANY_PEAKS:

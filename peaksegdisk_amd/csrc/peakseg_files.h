@@ -76,6 +76,7 @@ struct FileProblem {
   double penalty = 0.0;
   int cov = -1;      /* index into the parsed-coverage table */
   int dp_index = -1; /* index into the device problem set, -1 = trivial/none */
+  int shard = -1;    /* PEAKSEG_HIP_DEVICES: the shard that solved its program, -1 = none */
   bool outputs_opened = false;
   bool loss_failed = false, segments_failed = false;
   /* what the loss file says (kept for PeakSegFPOP_dir_batch / the penalty search) */
@@ -234,7 +235,170 @@ std::string real_path(const std::string &path) {
   return path;
 }
 
-int solve_files(int n, FileProblem *fps) {
+/* ---- PEAKSEG_HIP_DEVICES: one problem set per shard, one host thread per shard ---------- */
+
+/* Longest-processing-time-first dealing, as parallel.shard_problems: by cost descending (ties
+ * by index), each item to the least-loaded shard (ties by shard index); each shard ascending. */
+std::vector<std::vector<int>> deal_lpt(const std::vector<double> &cost, int n_shards) {
+  std::vector<int> order(cost.size());
+  for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
+  std::sort(order.begin(), order.end(), [&](int a, int b) {
+    return cost[(size_t)a] != cost[(size_t)b] ? cost[(size_t)a] > cost[(size_t)b] : a < b;
+  });
+  std::vector<double> load((size_t)n_shards, 0.0);
+  std::vector<std::vector<int>> shards((size_t)n_shards);
+  for (int i : order) {
+    size_t r = 0;
+    for (size_t k = 1; k < load.size(); k++)
+      if (load[k] < load[r]) r = k;
+    shards[r].push_back(i);
+    load[r] += cost[(size_t)i];
+  }
+  for (auto &s : shards) std::sort(s.begin(), s.end());
+  return shards;
+}
+
+/* what a shard thread leaves for the calling thread */
+struct ShardResult {
+  bool failed = false;
+  std::string error, warning;
+  ShardClock clock;
+};
+
+/* work(s) for every non-empty shard s, each on a host thread of its own pinned to devices[s];
+ * the calling thread prints their text while it waits.  Afterwards the calling thread reports
+ * the first failing shard's error and the first warning, in shard order, and the fan-out. */
+template <class Work>
+void run_shards(const std::vector<int> &devices, const std::vector<std::vector<int>> &shards,
+                std::vector<ShardResult> &results, Work work) {
+  const size_t S = devices.size();
+  results.assign(S, ShardResult());
+  ShardText text;
+  text.buf.resize(S);
+  std::vector<std::thread> threads;
+  for (size_t s = 0; s < S; s++) {
+    if (shards[s].empty()) continue;
+    text.running++;
+    threads.emplace_back([&, s]() {
+      g_shard_text = &text;
+      g_shard_index = (int)s;
+      g_shard_device = devices[s];
+      g_shard_clock = &results[s].clock;
+      work((int)s);
+      results[s].error = g_last_error;
+      results[s].warning = g_last_warning;
+      g_shard_clock = nullptr;
+      g_shard_device = -1;
+      g_shard_text = nullptr;
+      text.shard_done();
+    });
+  }
+  text.drain();
+  for (auto &th : threads) th.join();
+  bool have_error = false, have_warning = false;
+  g_last_warning.clear();
+  for (size_t s = 0; s < S; s++) {
+    if (results[s].failed && !have_error) {
+      g_last_error = results[s].error;
+      have_error = true;
+    }
+    if (!results[s].warning.empty() && !have_warning) {
+      g_last_warning = results[s].warning;
+      have_warning = true;
+    }
+  }
+  g_fanout.device = devices;
+  g_fanout.programs.clear();
+  g_fanout.seconds.clear();
+  for (size_t s = 0; s < S; s++) {
+    g_fanout.programs.push_back(results[s].clock.programs);
+    g_fanout.seconds.push_back(results[s].clock.seconds());
+    if (getenv("PEAKSEG_HIP_TIMING"))
+      fprintf(stderr, "peakseg_hip timing: shard %zu on device %d: %d programs, create %.3f s, "
+                      "solve %.3f s, fetch %.3f s\n", s, devices[s], results[s].clock.programs,
+              results[s].clock.create_s, results[s].clock.solve_s, results[s].clock.fetch_s);
+  }
+}
+
+/* Step 3 of solve_files under PEAKSEG_HIP_DEVICES: the device programs (prob_contig / prob_pen,
+ * first appearance order) dealt to one shard per listed device by predicted cost -- bins x the
+ * default ramp of parallel.predicted_cost over the program's penalty rank -- and each shard's
+ * programs solved in a problem set of its own that uploads only its own contigs (pointers into
+ * the caller's parsed coverage, not copies).  The set lives under its device's mutex, so the
+ * shards of distinct devices run concurrently and those of one device one after the other.
+ * Results land in fetched[program]; returns the shard of each program. */
+std::vector<int> solve_shards(const std::vector<int> &devices, const std::vector<int> &contig_n,
+                              const std::vector<const int *> &cnt_ptr,
+                              const std::vector<const int *> &wt_ptr,
+                              const std::vector<int> &prob_contig,
+                              const std::vector<double> &prob_pen,
+                              std::vector<DpFetched> &fetched) {
+  const size_t P = prob_contig.size();
+  std::vector<double> pens(prob_pen);
+  std::sort(pens.begin(), pens.end());
+  pens.erase(std::unique(pens.begin(), pens.end()), pens.end());
+  const double span = std::max(1.0, (double)pens.size() - 1.0);
+  std::vector<double> cost(P);
+  for (size_t k = 0; k < P; k++) {
+    const double rank =
+        (double)(std::lower_bound(pens.begin(), pens.end(), prob_pen[k]) - pens.begin());
+    cost[k] = (double)contig_n[(size_t)prob_contig[k]] * (19000.0 + 9000.0 * rank / span);
+  }
+  const std::vector<std::vector<int>> shards = deal_lpt(cost, (int)devices.size());
+  std::vector<int> shard_of(P, -1);
+  for (size_t s = 0; s < shards.size(); s++)
+    for (int k : shards[s]) shard_of[(size_t)k] = (int)s;
+  std::vector<ShardResult> results;
+  run_shards(devices, shards, results, [&](int s) {
+    const std::vector<int> &progs = shards[(size_t)s];
+    ShardClock &clock = results[(size_t)s].clock;
+    std::vector<int> local_of(contig_n.size(), -1), n_bins, contig;
+    std::vector<const int *> cnt, wt;
+    std::vector<double> pen;
+    for (int k : progs) {
+      const int c = prob_contig[(size_t)k];
+      if (local_of[(size_t)c] < 0) {
+        local_of[(size_t)c] = (int)n_bins.size();
+        n_bins.push_back(contig_n[(size_t)c]);
+        cnt.push_back(cnt_ptr[(size_t)c]);
+        wt.push_back(wt_ptr[(size_t)c]);
+      }
+      contig.push_back(local_of[(size_t)c]);
+      pen.push_back(prob_pen[(size_t)k]);
+    }
+    std::lock_guard<std::mutex> hold(device_mutex(devices[(size_t)s]));
+    double t = wall_now();
+    psd_problem_set *set = nullptr;
+    int st = peakseg_hip_problem_set_create(devices[(size_t)s], (int)n_bins.size(), n_bins.data(),
+                                            cnt.data(), wt.data(), (int)contig.size(),
+                                            contig.data(), pen.data(), 0, &set);
+    clock.create_s = wall_now() - t;
+    t = wall_now();
+    if (st == 0) {
+      st = peakseg_hip_problem_set_solve(set, nullptr, nullptr);
+      if (st == ERROR_DEVICE_SOLVER) st = 0; /* per-problem statuses decide below */
+    }
+    clock.solve_s = wall_now() - t;
+    t = wall_now();
+    bool failed = st != 0;
+    for (size_t j = 0; j < progs.size(); j++) {
+      DpFetched &f = fetched[(size_t)progs[j]];
+      if (st) {
+        f.status = st;
+      } else {
+        fetch_dp((int)j, set, f);
+      }
+      failed = failed || f.status != 0;
+    }
+    if (set) peakseg_hip_problem_set_destroy(set);
+    clock.fetch_s = wall_now() - t;
+    clock.programs = (int)progs.size();
+    results[(size_t)s].failed = failed;
+  });
+  return shard_of;
+}
+
+int solve_files(int n, FileProblem *fps, bool fan_out) {
   /* PEAKSEG_HIP_TIMING=1: where a call spends its time, on stderr */
   const bool timing = getenv("PEAKSEG_HIP_TIMING") != nullptr;
   double t_mark = wall_now();
@@ -302,7 +466,8 @@ int solve_files(int n, FileProblem *fps) {
       dp.push_back(i);
     }
   }
-  /* 3. all dynamic programs in one device problem set */
+  /* 3. all dynamic programs in one device problem set (PEAKSEG_HIP_DEVICES, in a batch entry
+   *    point: in one set per shard) */
   if (!dp.empty()) {
     std::vector<int> contig_of_cov(covs.size(), -1);
     std::vector<int> contig_n, prob_contig;
@@ -329,28 +494,56 @@ int solve_files(int n, FileProblem *fps) {
       prob_contig.push_back(contig_of_cov[(size_t)fp.cov]);
       prob_pen.push_back(fp.penalty);
     }
-    psd_problem_set *set = nullptr;
-    int st = peakseg_hip_problem_set_create(env_device(), (int)contig_n.size(), contig_n.data(),
+    std::vector<DpFetched> fetched(prob_contig.size());
+    std::vector<int> devices;
+    const int knob = fan_out && g_shard_device < 0 ? env_devices(devices) : 0;
+    if (!devices.empty()) {
+      const std::vector<int> shard_of =
+          solve_shards(devices, contig_n, cnt_ptr, wt_ptr, prob_contig, prob_pen, fetched);
+      for (int i : dp) fps[i].shard = shard_of[(size_t)fps[i].dp_index];
+      lap("upload + kernel + download, shards");
+    } else {
+      int device = 0;
+      int st = knob ? knob : env_device(device);
+      /* a shard thread's nested call (the search batch): its set holds the device's mutex */
+      std::unique_lock<std::mutex> hold;
+      if (st == 0 && g_shard_device >= 0) hold = std::unique_lock<std::mutex>(device_mutex(device));
+      double t_clock = wall_now();
+      psd_problem_set *set = nullptr;
+      if (st == 0)
+        st = peakseg_hip_problem_set_create(device, (int)contig_n.size(), contig_n.data(),
                                             cnt_ptr.data(), wt_ptr.data(), (int)prob_contig.size(),
                                             prob_contig.data(), prob_pen.data(), 0, &set);
-    lap("upload + allocate");
-    if (st == 0) {
-      st = peakseg_hip_problem_set_solve(set, nullptr, nullptr);
-      if (st == ERROR_DEVICE_SOLVER) st = 0; /* per-problem statuses decide below */
-    }
-    lap("kernel");
-    /* results leave the device one problem after the other; the text files (the segment
-     * tables of a penalty grid are hundreds of MB) are then formatted by a few threads */
-    std::vector<DpFetched> fetched(prob_contig.size());
-    for (size_t k = 0; k < fetched.size(); k++) {
-      if (st) {
-        fetched[k].status = st;
-      } else {
-        fetch_dp((int)k, set, fetched[k]);
+      lap("upload + allocate");
+      if (g_shard_clock) {
+        g_shard_clock->create_s += wall_now() - t_clock;
+        t_clock = wall_now();
+      }
+      if (st == 0) {
+        st = peakseg_hip_problem_set_solve(set, nullptr, nullptr);
+        if (st == ERROR_DEVICE_SOLVER) st = 0; /* per-problem statuses decide below */
+      }
+      lap("kernel");
+      if (g_shard_clock) {
+        g_shard_clock->solve_s += wall_now() - t_clock;
+        t_clock = wall_now();
+      }
+      /* results leave the device one problem after the other; the text files (the segment
+       * tables of a penalty grid are hundreds of MB) are then formatted by a few threads */
+      for (size_t k = 0; k < fetched.size(); k++) {
+        if (st) {
+          fetched[k].status = st;
+        } else {
+          fetch_dp((int)k, set, fetched[k]);
+        }
+      }
+      if (set) peakseg_hip_problem_set_destroy(set);
+      lap("download results + free");
+      if (g_shard_clock) {
+        g_shard_clock->fetch_s += wall_now() - t_clock;
+        g_shard_clock->programs += (int)prob_contig.size();
       }
     }
-    if (set) peakseg_hip_problem_set_destroy(set);
-    lap("download results + free");
     std::atomic<size_t> next_k{0};
     auto writer = [&]() {
       for (size_t k = next_k++; k < dp.size(); k = next_k++) {
@@ -387,6 +580,7 @@ int solve_files(int n, FileProblem *fps) {
       fp.bases = o.bases;
       fp.total_loss = o.total_loss;
       fp.db_bytes = o.db_bytes;
+      fp.shard = o.shard;
       /* its own database name, if it has one, is left as the first copy's is */
       if (fp.status == 0 && o.dp_index >= 0 && strcmp(fp.db, o.db) != 0 && touch_db(fp) &&
           truncate(fp.db, (off_t)fp.db_bytes) != 0)
@@ -571,8 +765,11 @@ struct ResidentDir {
         const int n = cv.n();
         const int *cnt = cv.count.data(), *wt = cv.weight.data();
         const int contig = 0;
-        st = peakseg_hip_problem_set_create(env_device(), 1, &n, &cnt, &wt, 1, &contig,
-                                            &fp.penalty, 0, &set);
+        int device = 0;
+        st = env_device(device);
+        if (st == 0)
+          st = peakseg_hip_problem_set_create(device, 1, &n, &cnt, &wt, 1, &contig, &fp.penalty, 0,
+                                              &set);
       } else {
         st = peakseg_hip_problem_set_set_penalty(set, 0, fp.penalty) == 0 ? 0 : ERROR_DEVICE_SOLVER;
       }
@@ -612,11 +809,13 @@ extern "C" int PeakSegFPOP_disk(char *bedGraph_file_name, char *penalty_str, cha
   fp.bedGraph = bedGraph_file_name;
   fp.penalty_str = penalty_str;
   fp.db = db_file_name;
-  return solve_files(1, &fp);
+  g_fanout.clear(1);
+  return solve_files(1, &fp, false);
 }
 
 extern "C" int PeakSegFPOP_disk_batch(int n_problems, char **bedGraph_files, char **penalty_strs,
                                       char **db_files, int *status_out) {
+  g_fanout.clear(n_problems);
   if (n_problems <= 0) return 0;
   std::vector<FileProblem> fps((size_t)n_problems);
   for (int i = 0; i < n_problems; i++) {
@@ -624,7 +823,8 @@ extern "C" int PeakSegFPOP_disk_batch(int n_problems, char **bedGraph_files, cha
     fps[(size_t)i].penalty_str = penalty_strs[i];
     fps[(size_t)i].db = db_files[i];
   }
-  int first = solve_files(n_problems, fps.data());
+  int first = solve_files(n_problems, fps.data(), true);
+  for (int i = 0; i < n_problems; i++) g_fanout.entry_shard[(size_t)i] = fps[(size_t)i].shard;
   if (status_out)
     for (int i = 0; i < n_problems; i++) status_out[i] = fps[(size_t)i].status;
   return first;
@@ -632,6 +832,7 @@ extern "C" int PeakSegFPOP_disk_batch(int n_problems, char **bedGraph_files, cha
 
 extern "C" int PeakSegFPOP_dir_batch(int n_problems, char **problem_dirs, char **penalty_strs,
                                      int *status_out, int *cached_out) {
+  g_fanout.clear(n_problems);
   if (n_problems <= 0) return 0;
   const double t0 = wall_now();
   std::vector<std::string> bedGraph((size_t)n_problems), norm((size_t)n_problems),
@@ -660,15 +861,19 @@ extern "C" int PeakSegFPOP_dir_batch(int n_problems, char **problem_dirs, char *
     fps[k].penalty_str = penalty_strs[i];
     fps[k].db = db[i].c_str();
   }
-  if (!todo.empty()) solve_files((int)fps.size(), fps.data());
+  if (!todo.empty()) solve_files((int)fps.size(), fps.data(), true);
+  for (size_t k = 0; k < todo.size(); k++) g_fanout.entry_shard[(size_t)todo[k]] = fps[k].shard;
   /* seconds: the reference times each call on its own; here the problems of a batch run
-   * concurrently, so each one is charged the batch's wall time in proportion to its data */
+   * concurrently, so each one is charged the batch's wall time in proportion to its data --
+   * among the problems of its own shard under PEAKSEG_HIP_DEVICES, whose shards run side by
+   * side (shard -1: no fan-out, or the problems no shard solved) */
   const double wall = wall_now() - t0;
-  double bins_total = 0.0;
-  for (auto &fp : fps) bins_total += fp.status == 0 ? (double)fp.bases : 0.0;
+  std::map<int, double> bins_of_shard;
+  for (auto &fp : fps) bins_of_shard[fp.shard] += fp.status == 0 ? (double)fp.bases : 0.0;
   for (size_t k = 0; k < todo.size(); k++) {
     const size_t i = (size_t)todo[k];
     FileProblem &fp = fps[k];
+    const double bins_total = bins_of_shard[fp.shard];
     const double megabytes = file_exists(db[i]) ? (double)fp.db_bytes / 1024.0 / 1024.0 : 0.0;
     unlink(db[i].c_str());
     if (fp.status == 0) {
@@ -778,11 +983,91 @@ void search_say_next(const std::vector<double> &next_pen) {
   emit_text("%s \n", line.c_str());
 }
 
+/* The lockstep rounds of PeakSegFPOP_sequential_search_batch over the directories dirs_of
+ * (all of them, or one shard's under PEAKSEG_HIP_DEVICES): each round computes the pending model
+ * of every active directory in one PeakSegFPOP_dir_batch call. */
+void search_rounds(const std::vector<int> &dirs_of, char **problem_dirs, std::vector<SearchState> &ss,
+                   const std::vector<std::string> &bedGraph, int verbose, int *n_rows,
+                   double t0, int &round, int &launches) {
+  for (;;) {
+    /* the models wanted now: (directory, row) pairs; a directory's first iteration asks for
+     * two (penalties 0 and Inf), later ones for one */
+    std::vector<int> who;
+    std::vector<psd_search_row *> row_of;
+    for (int d : dirs_of) {
+      SearchState &s = ss[(size_t)d];
+      if (!s.active()) continue;
+      if (verbose) {
+        emit_text("%s: ", problem_dirs[d]);
+        search_say_next(s.next_pen);
+      }
+      s.begin_iteration();
+      const std::vector<double> pens = s.next_pen;
+      for (double pen : pens) {
+        psd_search_row *r = s.new_row(pen);
+        if (!r) break;
+        who.push_back(d);
+        row_of.push_back(r);
+        s.n++; /* reserved; filled in below */
+      }
+      if (s.status) continue;
+      s.n = s.first_new; /* record() counts them again */
+    }
+    if (who.empty()) break;
+    round++;
+    /* drop the models of directories that have just failed */
+    std::vector<char *> dirs, pens;
+    std::vector<size_t> slot;
+    for (size_t k = 0; k < who.size(); k++) {
+      if (ss[(size_t)who[k]].status) continue;
+      dirs.push_back(problem_dirs[who[k]]);
+      pens.push_back(row_of[k]->penalty_str);
+      slot.push_back(k);
+    }
+    std::vector<int> st(dirs.size(), 0), cached(dirs.size(), 0);
+    if (!dirs.empty()) {
+      PeakSegFPOP_dir_batch((int)dirs.size(), dirs.data(), pens.data(), st.data(), cached.data());
+      launches++;
+    }
+    for (size_t j = 0; j < slot.size(); j++) {
+      const size_t k = slot[j];
+      const int d = who[k];
+      SearchState &s = ss[(size_t)d];
+      if (s.status) continue;
+      if (st[j]) {
+        s.status = st[j];
+        continue;
+      }
+      LossRow lr;
+      const std::string pre = bedGraph[(size_t)d] + "_penalty=" + row_of[k]->penalty_str;
+      if (!dir_cache_ok(bedGraph[(size_t)d], pre, lr)) {
+        set_error("sequential search: result files of %s are not consistent", pre.c_str());
+        s.status = ERROR_DEVICE_SOLVER;
+        continue;
+      }
+      s.record(*row_of[k], lr, cached[j] != 0);
+    }
+    for (int d : dirs_of) {
+      SearchState &s = ss[(size_t)d];
+      if (s.status || s.n == s.first_new || s.iteration == 0) continue;
+      bool mine = false;
+      for (size_t k = 0; k < who.size(); k++) mine = mine || who[k] == d;
+      if (!mine) continue;
+      if (n_rows) n_rows[d] = s.n;
+      s.end_iteration();
+    }
+    if (getenv("PEAKSEG_HIP_TIMING"))
+      fprintf(stderr, "peakseg_hip timing: search batch round %d: %zu models, %.1f s so far\n",
+              round, dirs.size(), wall_now() - t0);
+  }
+}
+
 }  // namespace
 
 extern "C" int PeakSegFPOP_sequential_search(const char *problem_dir, int peaks_int, int verbose,
                                              int row_capacity, psd_search_row *rows, int *n_rows,
                                              int *chosen_row) {
+  g_fanout.clear(1);
   if (n_rows) *n_rows = 0;
   if (chosen_row) *chosen_row = -1;
   if (!problem_dir || peaks_int < 0 || !rows || row_capacity < 2) {
@@ -840,6 +1125,7 @@ extern "C" int PeakSegFPOP_sequential_search_batch(int n_dirs, char **problem_di
                                                    int row_capacity, psd_search_row *rows,
                                                    int *n_rows, int *chosen_row,
                                                    int *status_out) {
+  g_fanout.clear(n_dirs);
   if (n_dirs <= 0) return 0;
   if (!problem_dirs || !peaks_int || !rows || row_capacity < 2) {
     set_error("sequential search: bad arguments");
@@ -865,76 +1151,42 @@ extern "C" int PeakSegFPOP_sequential_search_batch(int n_dirs, char **problem_di
       }
   const double t0 = wall_now();
   int round = 0, launches = 0;
-  for (;;) {
-    /* the models wanted now: (directory, row) pairs; a directory's first iteration asks for
-     * two (penalties 0 and Inf), later ones for one */
-    std::vector<int> who;
-    std::vector<psd_search_row *> row_of;
+  /* (a bad PEAKSEG_HIP_DEVICES: no shards, and the rounds' calls fail the dynamic programs) */
+  std::vector<int> devices;
+  if (g_shard_device < 0) env_devices(devices);
+  if (devices.empty()) {
+    std::vector<int> all((size_t)n_dirs);
+    for (int d = 0; d < n_dirs; d++) all[(size_t)d] = d;
+    search_rounds(all, problem_dirs, ss, bedGraph, verbose, n_rows, t0, round, launches);
+    g_fanout.clear(n_dirs);
+  } else {
+    /* the directories dealt by the byte size of their coverage.bedGraph; each shard runs the
+     * rounds of its own directories on a thread pinned to its device */
+    std::vector<int> live;
+    std::vector<double> cost;
     for (int d = 0; d < n_dirs; d++) {
-      SearchState &s = ss[(size_t)d];
-      if (!s.active()) continue;
-      if (verbose) {
-        emit_text("%s: ", problem_dirs[d]);
-        search_say_next(s.next_pen);
-      }
-      s.begin_iteration();
-      const std::vector<double> pens = s.next_pen;
-      for (double pen : pens) {
-        psd_search_row *r = s.new_row(pen);
-        if (!r) break;
-        who.push_back(d);
-        row_of.push_back(r);
-        s.n++; /* reserved; filled in below */
-      }
-      if (s.status) continue;
-      s.n = s.first_new; /* record() counts them again */
+      if (ss[(size_t)d].status) continue;
+      struct stat sb;
+      live.push_back(d);
+      cost.push_back(stat(bedGraph[(size_t)d].c_str(), &sb) == 0 ? (double)sb.st_size : 0.0);
     }
-    if (who.empty()) break;
-    round++;
-    /* drop the models of directories that have just failed */
-    std::vector<char *> dirs, pens;
-    std::vector<size_t> slot;
-    for (size_t k = 0; k < who.size(); k++) {
-      if (ss[(size_t)who[k]].status) continue;
-      dirs.push_back(problem_dirs[who[k]]);
-      pens.push_back(row_of[k]->penalty_str);
-      slot.push_back(k);
+    std::vector<std::vector<int>> shards = deal_lpt(cost, (int)devices.size());
+    for (auto &sh : shards)
+      for (int &j : sh) j = live[(size_t)j];
+    std::vector<int> rounds(devices.size(), 0), shard_launches(devices.size(), 0);
+    std::vector<ShardResult> results;
+    run_shards(devices, shards, results, [&](int sh) {
+      search_rounds(shards[(size_t)sh], problem_dirs, ss, bedGraph, verbose, n_rows, t0,
+                    rounds[(size_t)sh], shard_launches[(size_t)sh]);
+      for (int d : shards[(size_t)sh])
+        if (ss[(size_t)d].status) results[(size_t)sh].failed = true;
+    });
+    g_fanout.entry_shard.assign((size_t)n_dirs, -1);
+    for (size_t sh = 0; sh < shards.size(); sh++) {
+      for (int d : shards[sh]) g_fanout.entry_shard[(size_t)d] = (int)sh;
+      round = std::max(round, rounds[sh]);
+      launches += shard_launches[sh];
     }
-    std::vector<int> st(dirs.size(), 0), cached(dirs.size(), 0);
-    if (!dirs.empty()) {
-      PeakSegFPOP_dir_batch((int)dirs.size(), dirs.data(), pens.data(), st.data(), cached.data());
-      launches++;
-    }
-    for (size_t j = 0; j < slot.size(); j++) {
-      const size_t k = slot[j];
-      const int d = who[k];
-      SearchState &s = ss[(size_t)d];
-      if (s.status) continue;
-      if (st[j]) {
-        s.status = st[j];
-        continue;
-      }
-      LossRow lr;
-      const std::string pre = bedGraph[(size_t)d] + "_penalty=" + row_of[k]->penalty_str;
-      if (!dir_cache_ok(bedGraph[(size_t)d], pre, lr)) {
-        set_error("sequential search: result files of %s are not consistent", pre.c_str());
-        s.status = ERROR_DEVICE_SOLVER;
-        continue;
-      }
-      s.record(*row_of[k], lr, cached[j] != 0);
-    }
-    for (int d = 0; d < n_dirs; d++) {
-      SearchState &s = ss[(size_t)d];
-      if (s.status || s.n == s.first_new || s.iteration == 0) continue;
-      bool mine = false;
-      for (size_t k = 0; k < who.size(); k++) mine = mine || who[k] == d;
-      if (!mine) continue;
-      if (n_rows) n_rows[d] = s.n;
-      s.end_iteration();
-    }
-    if (getenv("PEAKSEG_HIP_TIMING"))
-      fprintf(stderr, "peakseg_hip timing: search batch round %d: %zu models, %.1f s so far\n",
-              round, dirs.size(), wall_now() - t0);
   }
   int first = 0;
   for (int d = 0; d < n_dirs; d++) {

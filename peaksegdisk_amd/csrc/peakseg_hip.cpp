@@ -84,7 +84,9 @@
 #undef PSD_CALL_LDS_OPS
 #undef PSD_PARK_ON_LDS_OVERFLOW
 
+#include <ctype.h>
 #include <errno.h>
+#include <limits.h>
 #include <algorithm>
 #include <math.h>
 #include <stdarg.h>
@@ -96,7 +98,10 @@
 
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <map>
+#include <memory>
+#include <mutex>
 #include <thread>
 #include <string>
 #include <vector>
@@ -132,16 +137,67 @@ void set_warning(const char *fmt, ...) {
   if (getenv("PEAKSEG_HIP_TIMING")) fprintf(stderr, "peakseg_hip warning: %s\n", buf);
 }
 
+void print_text(const char *text) {
+  if (g_print) {
+    g_print(text);
+  } else {
+    fputs(text, stdout);
+  }
+}
+
+/* Text of the shard threads of a fanned-out call (PEAKSEG_HIP_DEVICES).  g_print is R's Rprintf,
+ * which only R's own thread may call: a shard thread appends to its buffer, and the calling
+ * thread prints the complete lines (drain) while it waits and again after the join. */
+struct ShardText {
+  std::mutex m;
+  std::condition_variable cv; /* a line arrived, or a shard ended */
+  std::vector<std::string> buf;
+  int running = 0;
+
+  void append(int shard, const char *text) {
+    std::lock_guard<std::mutex> lk(m);
+    buf[(size_t)shard] += text;
+    if (strchr(text, '\n')) cv.notify_one();
+  }
+  void shard_done() {
+    std::lock_guard<std::mutex> lk(m);
+    running--;
+    cv.notify_one();
+  }
+  /* on the calling thread: print complete lines until every shard has ended, then the rest */
+  void drain() {
+    std::unique_lock<std::mutex> lk(m);
+    for (;;) {
+      const bool last = running == 0;
+      std::string out;
+      for (auto &b : buf) {
+        const size_t end = last ? b.size() : b.rfind('\n') + 1; /* npos + 1 == 0 */
+        out.append(b, 0, end);
+        b.erase(0, end);
+      }
+      if (!out.empty()) {
+        lk.unlock();
+        print_text(out.c_str());
+        lk.lock();
+      }
+      if (last) return;
+      cv.wait_for(lk, std::chrono::milliseconds(200));
+    }
+  }
+};
+thread_local ShardText *g_shard_text = nullptr;
+thread_local int g_shard_index = -1;
+
 void emit_text(const char *fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
-  if (g_print) {
-    g_print(buf);
+  if (g_shard_text) {
+    g_shard_text->append(g_shard_index, buf);
   } else {
-    fputs(buf, stdout);
+    print_text(buf);
   }
 }
 
@@ -747,15 +803,108 @@ int grow_ckpt_overflow_keep(psd_problem_set *s, unsigned long long pieces) {
   return 0;
 }
 
-int env_device() {
-  /* which GPU the file-level entry points use: PEAKSEG_HIP_DEVICE (one process per GPU sets it
-   * from its rank); default 0 */
+/* A shard thread of a fanned-out call: the device it is pinned to (-1 elsewhere).  Its nested
+ * file-level calls solve there and do not fan out again. */
+thread_local int g_shard_device = -1;
+
+/* PEAKSEG_HIP_DEVICES: the devices the batch entry points deal their programs to, "all" or a
+ * comma-separated list of ids (an id may repeat: its sets then run one after the other).
+ * Unset or empty: 0 and no devices.  A malformed list or an id that is not visible:
+ * ERROR_NO_HIP_DEVICE, with the offending entry and the visible count in last_error. */
+int env_devices(std::vector<int> &devices) {
+  devices.clear();
+  const char *e = getenv("PEAKSEG_HIP_DEVICES");
+  if (!e || !*e) return 0;
+  const int visible = peakseg_hip_device_count();
+  if (strcmp(e, "all") == 0) {
+    for (int d = 0; d < visible; d++) devices.push_back(d);
+    if (devices.empty()) {
+      set_error("PEAKSEG_HIP_DEVICES=all: no HIP device visible (this library has no CPU fallback)");
+      return ERROR_NO_HIP_DEVICE;
+    }
+    return 0;
+  }
+  for (const char *p = e;; p++) {
+    char *end = nullptr;
+    errno = 0;
+    const long d = isdigit((unsigned char)*p) ? strtol(p, &end, 10) : -1;
+    if (d < 0 || d > INT_MAX || errno || (*end != ',' && *end != 0)) {
+      devices.clear();
+      set_error("PEAKSEG_HIP_DEVICES=%s is not \"all\" or a comma-separated list of device ids "
+                "(%d HIP devices visible)", e, visible);
+      return ERROR_NO_HIP_DEVICE;
+    }
+    devices.push_back((int)d);
+    p = end;
+    if (*p == 0) break;
+  }
+  for (int d : devices)
+    if (d >= visible) {
+      devices.clear();
+      set_error("PEAKSEG_HIP_DEVICES=%s: no HIP device %d visible (%d HIP devices visible)", e, d,
+                visible);
+      return ERROR_NO_HIP_DEVICE;
+    }
+  return 0;
+}
+
+/* which GPU a single problem set of the file-level entry points uses: a shard thread's own
+ * device; else the first of PEAKSEG_HIP_DEVICES; else PEAKSEG_HIP_DEVICE (one process per GPU
+ * sets it from its rank), default 0.  ERROR_NO_HIP_DEVICE when PEAKSEG_HIP_DEVICES is bad. */
+int env_device(int &device) {
+  device = 0;
+  if (g_shard_device >= 0) {
+    device = g_shard_device;
+    return 0;
+  }
+  std::vector<int> devices;
+  const int st = env_devices(devices);
+  if (st || !devices.empty()) {
+    if (!st) device = devices[0];
+    return st;
+  }
   if (const char *e = getenv("PEAKSEG_HIP_DEVICE")) {
     int d = atoi(e);
-    if (d >= 0) return d;
+    if (d >= 0) device = d;
   }
   return 0;
 }
+
+/* One process-wide mutex per device id: a shard holds its device's from the creation of its
+ * problem set to its destruction, so that no two sets of this process run on one device at the
+ * same time (a solve's hipFree and arena growth synchronise the device). */
+std::mutex &device_mutex(int device) {
+  static std::mutex guard;
+  static std::map<int, std::unique_ptr<std::mutex>> locks;
+  std::lock_guard<std::mutex> lk(guard);
+  std::unique_ptr<std::mutex> &m = locks[device];
+  if (!m) m.reset(new std::mutex);
+  return *m;
+}
+
+/* What the calling thread's last file-level call did with PEAKSEG_HIP_DEVICES
+ * (peakseg_hip_last_fanout): one row per shard, and the shard of each entry (-1: none). */
+struct FanoutReport {
+  std::vector<int> device, programs;
+  std::vector<double> seconds;
+  std::vector<int> entry_shard;
+
+  void clear(int n_entries) {
+    device.clear();
+    programs.clear();
+    seconds.clear();
+    entry_shard.assign((size_t)(n_entries > 0 ? n_entries : 0), -1);
+  }
+};
+thread_local FanoutReport g_fanout;
+
+/* A shard's device time, accumulated by every problem set it creates */
+struct ShardClock {
+  int programs = 0;
+  double create_s = 0.0, solve_s = 0.0, fetch_s = 0.0;
+  double seconds() const { return create_s + solve_s + fetch_s; }
+};
+thread_local ShardClock *g_shard_clock = nullptr;
 
 }  // namespace
 
@@ -777,6 +926,24 @@ extern "C" int peakseg_hip_device_clock_khz(int device) {
 }
 
 extern "C" void peakseg_hip_set_print(void (*print)(const char *)) { g_print = print; }
+
+extern "C" int peakseg_hip_last_fanout(int capacity, int *shard_device, int *shard_programs,
+                                       double *shard_seconds) {
+  const int n = (int)g_fanout.device.size();
+  for (int s = 0; s < n && s < capacity; s++) {
+    if (shard_device) shard_device[s] = g_fanout.device[(size_t)s];
+    if (shard_programs) shard_programs[s] = g_fanout.programs[(size_t)s];
+    if (shard_seconds) shard_seconds[s] = g_fanout.seconds[(size_t)s];
+  }
+  return n;
+}
+
+extern "C" int peakseg_hip_last_fanout_entries(int n, int *shard_of) {
+  const int m = (int)g_fanout.entry_shard.size();
+  for (int i = 0; i < n && i < m; i++)
+    if (shard_of) shard_of[i] = g_fanout.entry_shard[(size_t)i];
+  return m;
+}
 
 extern "C" void peakseg_hip_problem_set_destroy(psd_problem_set *s) {
   if (!s) return;

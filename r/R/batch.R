@@ -2,12 +2,35 @@
 ### entry points of the package (PeakSegFPOP_file/_dir/_df/_vec, sequentialSearch_dir) keep
 ### working unchanged through .C("PeakSegFPOP_interface"); these are optional faster forms.
 
+set_devices_knob <- function
+### PEAKSEG_HIP_DEVICES for one call: NULL leaves the environment alone; "all" or device ids
+### (e.g. 0:7) spread the call over those GPUs.  Returns what restore_devices_knob needs.
+(devices){
+  if(is.null(devices))return(NULL)
+  old <- Sys.getenv("PEAKSEG_HIP_DEVICES", unset=NA)
+  Sys.setenv(PEAKSEG_HIP_DEVICES=paste(devices, collapse=","))
+  list(old=old)
+}
+
+restore_devices_knob <- function(saved){
+  if(is.null(saved))return(invisible())
+  if(is.na(saved$old)){
+    Sys.unsetenv("PEAKSEG_HIP_DEVICES")
+  }else{
+    Sys.setenv(PEAKSEG_HIP_DEVICES=saved$old)
+  }
+  invisible()
+}
+
 PeakSegFPOP_dir_batch <- function
 ### PeakSegFPOP_dir for many (problem.dir, penalty) pairs: cached results are reused, the rest
-### is solved in one launch (one parse and upload per coverage.bedGraph).
-(problem.dir.vec, penalty.vec){
+### is solved in one launch (one parse and upload per coverage.bedGraph).  devices: "all" or
+### GPU ids, one problem set per listed GPU, solved side by side.
+(problem.dir.vec, penalty.vec, devices=NULL){
   stopifnot(is.character(problem.dir.vec), length(problem.dir.vec)==length(penalty.vec))
   n <- length(problem.dir.vec)
+  saved <- set_devices_knob(devices)
+  on.exit(restore_devices_knob(saved), add=TRUE)
   res <- .C(
     "PeakSegFPOP_dir_batch_interface",
     as.character(problem.dir.vec), paste(penalty.vec), as.integer(n),
@@ -50,10 +73,13 @@ sequentialSearch_dir_resident <- function
 sequentialSearch_dir_batch <- function
 ### sequentialSearch_dir on several problem directories at once: every directory gets the
 ### result sequentialSearch_dir(problem.dir, peaks.int) gives, but the models the searches ask
-### for in the same iteration are computed in one launch on the GPU.
-(problem.dir.vec, peaks.int.vec, verbose=0){
+### for in the same iteration are computed in one launch on the GPU.  devices: "all" or GPU
+### ids, the directories dealt to one shard per listed GPU.
+(problem.dir.vec, peaks.int.vec, verbose=0, devices=NULL){
   stopifnot(is.character(problem.dir.vec), is.integer(peaks.int.vec), all(0 <= peaks.int.vec))
   n <- length(problem.dir.vec)
+  saved <- set_devices_knob(devices)
+  on.exit(restore_devices_knob(saved), add=TRUE)
   peaks.int.vec <- rep(peaks.int.vec, l=n)
   capacity <- 256L
   res <- .C(
