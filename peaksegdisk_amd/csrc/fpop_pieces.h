@@ -207,10 +207,11 @@ PSD_D PieceOpt piece_opt(const Coef &c) {
 
 /* fpl:29-50; caller guarantees c.Log != 0 (the reference throws otherwise) */
 PSD_D bool has_two_roots(const Coef &c, const PieceOpt &o, double equals) {
-  if (0 < c.Linear) {
-    return o.cost + NEWTON_EPSILON < equals && o.cost2 + NEWTON_EPSILON < equals;
-  }
-  return equals + NEWTON_EPSILON < o.cost && equals + NEWTON_EPSILON < o.cost2;
+  /* (both cases evaluated, '&' and a select: with '&&' and an 'if' every comparison of doubles
+   * became an exec-masked region of its own) */
+  const bool below = (o.cost + NEWTON_EPSILON < equals) & (o.cost2 + NEWTON_EPSILON < equals);
+  const bool above = (equals + NEWTON_EPSILON < o.cost) & (equals + NEWTON_EPSILON < o.cost2);
+  return (0 < c.Linear) ? below : above;
 }
 
 /* The reference's Newton loops (fpl:98-124,158-188) also track the closest iterate on each
@@ -287,8 +288,8 @@ PSD_D double get_larger_root(const Coef &c, const PieceOpt &o, double max_log_me
                              int *rare_out = nullptr) {
   double optimal_mean = o.mean;
   double optimal_cost = o.cost2;
-  if ((optimal_cost < right_cost && right_cost < equals) ||
-      (optimal_cost > right_cost && right_cost > equals)) {
+  if (((optimal_cost < right_cost) & (right_cost < equals)) |
+      ((optimal_cost > right_cost) & (right_cost > equals))) {
     return max_log_mean + 1;
   }
   double candidate_root = optimal_mean + 1;
@@ -342,8 +343,8 @@ PSD_D double get_smaller_root(const Coef &c, const PieceOpt &o, double min_log_m
                               double left_cost, double equals, int *steps_out = nullptr) {
   double optimal_log_mean = o.log_mean;
   double optimal_cost = o.cost;
-  if ((equals < left_cost && left_cost < optimal_cost) ||
-      (equals > left_cost && left_cost > optimal_cost)) {
+  if (((equals < left_cost) & (left_cost < optimal_cost)) |
+      ((equals > left_cost) & (left_cost > optimal_cost))) {
     return min_log_mean - 1;
   }
   double candidate_root = optimal_log_mean - 1;
@@ -389,8 +390,8 @@ PSD_D double get_smaller_root(const Coef &c, const PieceOpt &o, double min_log_m
 
 /* fpl:862-868 */
 PSD_D bool same_funs(const Coef &a, const Coef &b) {
-  return a.Linear == b.Linear && a.Log == b.Log &&
-         absd(a.Constant - b.Constant) < NEWTON_EPSILON;
+  return (a.Linear == b.Linear) & (a.Log == b.Log) &
+         (absd(a.Constant - b.Constant) < NEWTON_EPSILON);
 }
 
 }  // namespace PSD_VARIANT

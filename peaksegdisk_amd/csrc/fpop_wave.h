@@ -512,29 +512,20 @@ PSD_D bool min_less_pre(const L &in, int n, const S &s, LanePiece &P, M &mth, in
       double lc = s.lc(i), rc = s.rc(i);
       bool has_next = i + 1 < n;
       double next_left_cost = has_next ? s.lc(i + 1) : PSD_INF;
-      int cls;
-      if (Log_i == 0) { /* fpl:256-308 */
-        double right_left_diff = rc - lc;
-        bool right_left_equal = right_left_diff < NEWTON_EPSILON;
-        bool next_cost_more_than_left = true;
-        if (has_next) {
-          double next_left_diff = next_left_cost - lc;
-          next_cost_more_than_left = NEWTON_EPSILON < next_left_diff;
-        }
-        cls = (next_cost_more_than_left && !right_left_equal) ? CLS_CONST_EDGE : CLS_STORE;
-      } else { /* fpl:309-366 */
-        double mu = s.mu(i), mu_cost = s.muc(i);
-        bool next_ok = true;
-        if (has_next) next_ok = NEWTON_EPSILON < next_left_cost - mu_cost;
-        bool cost_ok = NEWTON_EPSILON < rc - mu_cost && next_ok;
-        if (mu <= in.mn(i) && cost_ok) {
-          cls = CLS_CONST_EDGE;
-        } else if (mu < in.mx(i) && cost_ok) {
-          cls = CLS_CONST_MU;
-        } else {
-          cls = CLS_STORE;
-        }
-      }
+      /* both kinds of piece are classified and one result selected: all reads in one LDS
+       * round trip and no exec-masked region per test (a degenerate piece's optimum is stored
+       * as zeros) */
+      const double mu = s.mu(i), mu_cost = s.muc(i), mn_i = in.mn(i), mx_i = in.mx(i);
+      /* fpl:256-308 */
+      const bool right_left_equal = rc - lc < NEWTON_EPSILON;
+      const bool next_cost_more_than_left = !has_next | (NEWTON_EPSILON < next_left_cost - lc);
+      const int cls_flat = (next_cost_more_than_left & !right_left_equal) ? CLS_CONST_EDGE : CLS_STORE;
+      /* fpl:309-366 */
+      const bool next_ok = !has_next | (NEWTON_EPSILON < next_left_cost - mu_cost);
+      const bool cost_ok = (NEWTON_EPSILON < rc - mu_cost) & next_ok;
+      int cls_convex = ((mu < mx_i) & cost_ok) ? CLS_CONST_MU : CLS_STORE;
+      cls_convex = ((mu <= mn_i) & cost_ok) ? CLS_CONST_EDGE : cls_convex;
+      const int cls = (Log_i == 0) ? cls_flat : cls_convex;
       s.cls(i) = cls;
       if (base == 0) P.cls = cls;
     }
@@ -560,26 +551,17 @@ PSD_D bool min_more_pre(const L &in, int n, const S &s, LanePiece &P, M &mth, in
   for (int base = 0; base < n; base += WAVE) {
     int i = base + lane;
     if (i < n) {
-      int cls;
-      if (in.Log(i) == 0) { /* fpl:458-467 */
-        cls = CLS_STORE;
-      } else { /* fpl:468-548 */
-        double mu = s.mu(i), mu_cost = s.muc(i);
-        bool prev_ok = true;
-        if (i > 0) {
-          double prev_cost_right = s.rc(i - 1);
-          prev_ok = NEWTON_EPSILON < prev_cost_right - mu_cost;
-        }
-        double this_cost_left = s.lc(i);
-        if (in.mx(i) <= mu) {
-          double this_cost_diff = this_cost_left - s.rc(i);
-          cls = (NEWTON_EPSILON < this_cost_diff) ? CLS_CONST_EDGE : CLS_STORE;
-        } else if (in.mn(i) < mu && NEWTON_EPSILON < this_cost_left - mu_cost && prev_ok) {
-          cls = CLS_CONST_MU;
-        } else {
-          cls = CLS_STORE;
-        }
-      }
+      /* (selects, all reads in one LDS round trip: as in min_less_pre) */
+      const double Log_i = in.Log(i), mu = s.mu(i), mu_cost = s.muc(i);
+      const double mn_i = in.mn(i), mx_i = in.mx(i);
+      const double this_cost_left = s.lc(i), this_cost_right = s.rc(i);
+      const double prev_cost_right = s.rc(i > 0 ? i - 1 : 0);
+      /* fpl:468-548 */
+      const bool prev_ok = (i <= 0) | (NEWTON_EPSILON < prev_cost_right - mu_cost);
+      const int cls_edge = (NEWTON_EPSILON < this_cost_left - this_cost_right) ? CLS_CONST_EDGE : CLS_STORE;
+      const bool at_mu = (mn_i < mu) & (NEWTON_EPSILON < this_cost_left - mu_cost) & prev_ok;
+      const int cls_convex = (mx_i <= mu) ? cls_edge : (at_mu ? CLS_CONST_MU : CLS_STORE);
+      const int cls = (Log_i == 0) ? CLS_STORE : cls_convex; /* fpl:458-467 */
       s.cls(i) = cls;
       if (base == 0) P.cls = cls;
     }
@@ -675,20 +657,21 @@ PSD_D int min_less_impl(L in_, int n_, L out_, int cap_, S s_, int data_i_out_,
     if (spec) {
       bool inside = false, at_right = false, bad = false;
       int sp_steps = 0;
-      if (tj >= 0) {
-        double level = (s.cls(tj) == CLS_CONST_MU) ? s.muc(tj) : s.lc(tj);
-        Coef c = load_coef(in, tk);
-        if (c.Log == 0) {
-          if (c.Linear < 0) bad = true; /* fpl:378-380 */
-        } else {
-          PieceOpt o = {s.om(tk), s.mu(tk), s.muc(tk), s.oc2(tk)};
-          if (has_two_roots(c, o, level)) {
-            sp_mu = get_smaller_root(c, o, in.mn(tk), s.lc(tk), level, &sp_steps);
-            inside = in.mn(tk) < sp_mu && sp_mu < in.mx(tk);
-          }
-          if (!inside) at_right = s.rc(tk) <= level + NEWTON_EPSILON;
-        }
+      /* every lane loads (a lane without a task reads piece 0: harmless), so that all reads
+       * share one LDS round trip and the only exec-masked region is the Newton solve */
+      const bool task = tj >= 0;
+      const int sj = task ? tj : 0;
+      const double level = (s.cls(sj) == CLS_CONST_MU) ? s.muc(sj) : s.lc(sj);
+      const Coef c = load_coef(in, tk);
+      const PieceOpt o = {s.om(tk), s.mu(tk), s.muc(tk), s.oc2(tk)};
+      const double t_mn = in.mn(tk), t_mx = in.mx(tk), t_lc = s.lc(tk), t_rc = s.rc(tk);
+      const bool convex = task & (c.Log != 0);
+      bad = task & (c.Log == 0) & (c.Linear < 0); /* fpl:378-380 */
+      if (convex & has_two_roots(c, o, level)) {
+        sp_mu = get_smaller_root(c, o, t_mn, t_lc, level, &sp_steps);
+        inside = (t_mn < sp_mu) & (sp_mu < t_mx);
       }
+      at_right = convex & !inside & (t_rc <= level + NEWTON_EPSILON);
       PSD_PROF_ITERS(PROF_IT_SPEC, sp_steps);
       sp_ev = ballot(inside || at_right);
       sp_inside = ballot(inside);
@@ -1586,19 +1569,16 @@ PSD_D void env_classify_lanes(bool valid, const Coef &c1, const Coef &c2, double
   /* phase G, the part that needs both roots */
   if (!EARLY_TAIL && neither && two_roots) e_smaller = mth.exp(smaller_log_mean);
   double first_log_mean = PSD_INF, second_log_mean = PSD_INF;
-  if (neither && two_roots) {
-    bool larger_inside = a < larger_log_mean && larger_log_mean < b;
-    bool smaller_inside = a < smaller_log_mean && 0 < e_smaller && smaller_log_mean < b;
-    if (larger_inside) {
-      if (smaller_inside && smaller_log_mean < larger_log_mean) {
-        first_log_mean = smaller_log_mean;
-        second_log_mean = larger_log_mean;
-      } else {
-        first_log_mean = larger_log_mean;
-      }
-    } else if (smaller_inside) {
-      first_log_mean = smaller_log_mean;
-    }
+  { /* which roots are crossings inside (a, b), in order: selects, no region per case */
+    const bool on = neither & two_roots;
+    const bool larger_inside = on & (a < larger_log_mean) & (larger_log_mean < b);
+    const bool smaller_inside =
+        on & (a < smaller_log_mean) & (0 < e_smaller) & (smaller_log_mean < b);
+    const bool both_inside = larger_inside & smaller_inside & (smaller_log_mean < larger_log_mean);
+    first_log_mean = smaller_inside ? smaller_log_mean : first_log_mean;
+    first_log_mean = larger_inside ? larger_log_mean : first_log_mean;
+    first_log_mean = both_inside ? smaller_log_mean : first_log_mean;
+    second_log_mean = both_inside ? larger_log_mean : second_log_mean;
   }
   const bool crossing = neither && first_log_mean != PSD_INF;
   const bool two = crossing && second_log_mean != PSD_INF;
@@ -1628,72 +1608,72 @@ PSD_D void env_classify_lanes(bool valid, const Coef &c1, const Coef &c2, double
   }
 
   PSD_PROF_ADD(PROF_C_TAIL);
-  /* ---- decisions (no more transcendentals) ---- */
-  if (!valid) return;
+  /* ---- decisions (no more transcendentals) ----
+   * The decision tree of push_min_pieces as values: every case's shape (1-3 pieces), first
+   * source and crossing is computed by comparisons of values that all lanes hold, and the tree
+   * only selects among them, innermost case first -- no exec-masked region per case.  A
+   * one-piece shape is dropped when the interval is empty (cand_one). */
   const int by_mid = cost_diff_mid < 0 ? 0 : 1;
-  if (triv) {
-    cand_one(out, 0, a, b);
-  } else if (both) { /* fpl:963-971 */
-    cand_one(out, by_mid, a, b);
-  } else if (degen) {
-    if (d.Linear == 0) {
-      cand_one(out, d.Constant < 0 ? 0 : 1, a, b);
-    } else if (d.Constant == 0) {
-      cand_one(out, d.Linear < 0 ? 0 : 1, a, b);
-    } else if (a < lres && lres < b) {
-      cand_two(out, (0 < d.Linear) ? 0 : 1, lres);
-    } else {
-      cand_one(out, by_mid, a, b);
-    }
-  } else if (same_at_right) { /* fpl:1029-1093 */
-    if (two_roots) {
-      double x = smaller_log_mean, opt = o.log_mean;
-      if (a < x && x < opt && opt < b) {
-        cand_two(out, (cost_diff_left < 0) ? 0 : 1, x);
-      } else {
-        bool it1_smaller_at_mean0 = 0 < d.Log;
-        if (x < a) {
-          cand_one(out, it1_smaller_at_mean0 ? 1 : 0, a, b);
-        } else {
-          cand_one(out, it1_smaller_at_mean0 ? 0 : 1, a, b);
-        }
-      }
-    } else {
-      cand_one(out, by_mid, a, b);
-    }
-  } else if (same_at_left) { /* fpl:1094-1123 */
-    double x = larger_log_mean, opt = o.log_mean;
-    if (two_roots && a < opt && opt < x && x < b) {
-      cand_two(out, (cost_diff_right < 0) ? 1 : 0, x);
-    } else {
-      cand_one(out, by_mid, a, b);
-    }
-  } else if (two) { /* fpl:1171-1205 */
-    bool it1_larger_before = need_before ? (cost_diff_before < 0) : !(cost_diff_other < 0);
-    cand_three(out, it1_larger_before ? 0 : 1, first_log_mean, second_log_mean);
-  } else if (crossing) { /* fpl:1206-1237 */
-    if (cost_diff_before < 0) {
-      if (cost_diff_other < 0) {
-        cand_one(out, 0, a, b);
-      } else {
-        cand_two(out, 0, first_log_mean);
-      }
-    } else {
-      if (cost_diff_other < 0) {
-        cand_two(out, 1, first_log_mean);
-      } else {
-        cand_one(out, 1, a, b);
-      }
-    }
-  } else { /* fpl:1238-1258 */
-    double cost_diff;
-    if (absd(cost_diff_mid) < NEWTON_EPSILON) {
-      cost_diff = cost_diff_right;
-    } else {
-      cost_diff = cost_diff_mid;
-    }
-    cand_one(out, cost_diff < 0 ? 0 : 1, a, b);
+  const int one = (b <= a) ? 0 : 1; /* cand_one's n */
+  /* fpl:1238-1258: no crossing inside */
+  const int by_ends = ((absd(cost_diff_mid) < NEWTON_EPSILON) ? cost_diff_right : cost_diff_mid) < 0 ? 0 : 1;
+  int n = one, first = by_ends;
+  double x1 = 0.0, x2 = 0.0;
+  { /* fpl:1206-1237: one crossing */
+    const bool before = cost_diff_before < 0, other = cost_diff_other < 0;
+    const bool split = before != other;
+    n = crossing ? (split ? 2 : one) : n;
+    first = crossing ? (before ? 0 : 1) : first;
+    x1 = (crossing & split) ? first_log_mean : x1;
   }
+  { /* fpl:1171-1205: two crossings */
+    const bool it1_larger_before = need_before ? (cost_diff_before < 0) : !(cost_diff_other < 0);
+    n = two ? 3 : n;
+    first = two ? (it1_larger_before ? 0 : 1) : first;
+    x1 = two ? first_log_mean : x1;
+    x2 = two ? second_log_mean : x2;
+  }
+  { /* fpl:1094-1123 */
+    const double x = larger_log_mean, opt = o.log_mean;
+    const bool cut = two_roots & (a < opt) & (opt < x) & (x < b);
+    n = same_at_left ? (cut ? 2 : one) : n;
+    first = same_at_left ? (cut ? ((cost_diff_right < 0) ? 1 : 0) : by_mid) : first;
+    x1 = same_at_left ? (cut ? x : 0.0) : x1;
+    x2 = same_at_left ? 0.0 : x2;
+  }
+  { /* fpl:1029-1093 */
+    const double x = smaller_log_mean, opt = o.log_mean;
+    const bool cut = two_roots & (a < x) & (x < opt) & (opt < b);
+    const bool it1_smaller_at_mean0 = 0 < d.Log;
+    const int side = ((x < a) == it1_smaller_at_mean0) ? 1 : 0;
+    const int f_cut = !(cost_diff_left < 0), f_whole = two_roots ? side : by_mid;
+    const int f = cut ? f_cut : f_whole;
+    n = same_at_right ? (cut ? 2 : one) : n;
+    first = same_at_right ? f : first;
+    x1 = same_at_right ? (cut ? x : 0.0) : x1;
+    x2 = same_at_right ? 0.0 : x2;
+  }
+  { /* fpl:973-1019 */
+    const bool cut = (d.Linear != 0) & (d.Constant != 0) & (a < lres) & (lres < b);
+    const int f_lin0 = !(d.Constant < 0), f_con0 = !(d.Linear < 0), f_cut = !(0 < d.Linear);
+    int f = cut ? f_cut : by_mid;
+    f = (d.Constant == 0) ? f_con0 : f;
+    f = (d.Linear == 0) ? f_lin0 : f;
+    n = degen ? (cut ? 2 : one) : n;
+    first = degen ? f : first;
+    x1 = degen ? (cut ? lres : 0.0) : x1;
+    x2 = degen ? 0.0 : x2;
+  }
+  /* fpl:963-971, fpl:945-951 */
+  const bool flat = triv | both;
+  n = flat ? one : n;
+  first = triv ? 0 : (both ? by_mid : first);
+  x1 = flat ? 0.0 : x1;
+  x2 = flat ? 0.0 : x2;
+  out.n = valid ? n : 0;
+  out.first = valid ? first : 0;
+  out.x1 = valid ? x1 : 0.0;
+  out.x2 = valid ? x2 : 0.0;
 }
 
 /* Loads merged interval (i1,i2): the two pieces and the interval [a,b] (fpl:876-932 without
@@ -1706,10 +1686,12 @@ PSD_D void env_load_interval(const L &f1, int n1, const L &f2, int n2, int i1, i
   double mn1 = f1.mn(i1), mx1 = f1.mx(i1), mn2 = f2.mn(i2), mx2 = f2.mx(i2);
   /* the piece that started earlier / ends later must have a neighbour on that side; the
    * reference would read a std::list sentinel otherwise */
-  bool sentinel = (mn1 < mn2 && i2 == 0) || (mn2 < mn1 && i1 == 0) ||
-                  (mn1 == mn2 && (i1 == 0) != (i2 == 0)) || (mx1 < mx2 && i1 + 1 >= n1) ||
-                  (mx2 < mx1 && i2 + 1 >= n2) ||
-                  (mx1 == mx2 && (i1 + 1 == n1) != (i2 + 1 == n2));
+  /* ('&' and '|': every term is a comparison of values already loaded, and short-circuit
+   * evaluation made each an exec-masked region) */
+  bool sentinel = ((mn1 < mn2) & (i2 == 0)) | ((mn2 < mn1) & (i1 == 0)) |
+                  ((mn1 == mn2) & ((i1 == 0) != (i2 == 0))) | ((mx1 < mx2) & (i1 + 1 >= n1)) |
+                  ((mx2 < mx1) & (i2 + 1 >= n2)) |
+                  ((mx1 == mx2) & ((i1 + 1 == n1) != (i2 + 1 == n2)));
   a = mn1 < mn2 ? mn2 : mn1;
   b = mx1 < mx2 ? mx1 : mx2;
   if (sentinel) err |= WERR_SENTINEL;
@@ -1744,13 +1726,13 @@ PSD_D void env_neighbour_flags(const L &f1, const L &f2, const S &s, int k, int 
 /* push_piece's "same as last" test (fpl:1270-1273) */
 PSD_D bool coalesces(const Coef &last, double last_prv, int last_di, const Coef &c, double prv,
                      int di) {
-  return same_funs(last, c) && prv == last_prv && di == last_di;
+  return same_funs(last, c) & (prv == last_prv) & (di == last_di);
 }
 PSD_D bool bit_identical(const Coef &last, double last_prv, int last_di, const Coef &c,
                          double prv, int di) {
-  return psd_d2u(last.Linear) == psd_d2u(c.Linear) && psd_d2u(last.Log) == psd_d2u(c.Log) &&
-         psd_d2u(last.Constant) == psd_d2u(c.Constant) && psd_d2u(last_prv) == psd_d2u(prv) &&
-         last_di == di;
+  return (psd_d2u(last.Linear) == psd_d2u(c.Linear)) & (psd_d2u(last.Log) == psd_d2u(c.Log)) &
+         (psd_d2u(last.Constant) == psd_d2u(c.Constant)) & (psd_d2u(last_prv) == psd_d2u(prv)) &
+         (last_di == di);
 }
 
 #ifdef PSD_HELPER_WAVES
@@ -2033,24 +2015,18 @@ PSD_D int min_env_impl(L f1_, int n1_, L f2_, int n2_, L out_, int cap_, S s_, i
     int pid = shfl_i(my_last_id, below ? msb64(below) : 0); /* per-lane source */
     if (!below) pid = last_id;
     const bool have_pred = pid >= 0;
-    Coef pc = {0.0, 0.0, 0.0};
-    double pprv = 0.0;
-    int pdi = 0;
-    if (has && have_pred) {
-      const L &pl = (pid >> 20) ? f2 : f1;
-      const int pi = pid & 0xfffff;
-      pc = load_coef(pl, pi);
-      pprv = pl.prv(pi);
-      pdi = pl.di(pi);
-    }
-    bool head0 = true; /* does the first candidate start a new output piece? */
-    bool fuzzy = false;
-    if (has && have_pred) {
-      bool co = coalesces(pc, pprv, pdi, fc, fprv, fdi);
-      bool bi = bit_identical(pc, pprv, pdi, fc, fprv, fdi);
-      head0 = !co;
-      fuzzy = co && !bi;
-    }
+    /* (every lane reads a predecessor -- piece 0 where it has none -- and the tests are masked
+     * afterwards: one LDS round trip, no exec-masked region) */
+    const L &pl = (have_pred && (pid >> 20)) ? f2 : f1;
+    const int pi = have_pred ? (pid & 0xfffff) : 0;
+    const Coef pc = load_coef(pl, pi);
+    const double pprv = pl.prv(pi);
+    const int pdi = pl.di(pi);
+    const bool follows = has & have_pred;
+    const bool co = follows & coalesces(pc, pprv, pdi, fc, fprv, fdi);
+    const bool bi = bit_identical(pc, pprv, pdi, fc, fprv, fdi);
+    const bool head0 = !co; /* does the first candidate start a new output piece? */
+    const bool fuzzy = co & !bi;
     /* candidates 2 and 3 of a lane alternate it1/it2 with same_funs(it1,it2) false, so
      * they always start a new piece -- provided the run they follow is bit-identical to
      * its head, which `fuzzy` checks. */
@@ -2065,25 +2041,22 @@ PSD_D int min_env_impl(L f1_, int n1_, L f2_, int n2_, L out_, int cap_, S s_, i
     int heads_total = popc64(hb0) + 2 * popc64(hb1);
     if (n_out + heads_total > cap) return -WERR_OVERFLOW;
     int slot = n_out + heads_before - (head0 ? 0 : 1); /* piece candidate 0 belongs to */
-    if (has) {
-      if (head0) store_piece(out, slot, fc, ia, hi0, fdi, fprv);
-      if (cd.n >= 2) {
-        Coef c = src1 ? c2 : c1;
-        store_piece(out, slot + 1, c, cd.x1, hi1, src1 ? di2 : di1, src1 ? prv2 : prv1);
-      }
-      if (cd.n >= 3) store_piece(out, slot + 2, fc, cd.x2, ib, fdi, fprv);
+    if (has & head0) store_piece(out, slot, fc, ia, hi0, fdi, fprv);
+    if (has & (cd.n >= 2)) {
+      Coef c = src1 ? c2 : c1;
+      store_piece(out, slot + 1, c, cd.x1, hi1, src1 ? di2 : di1, src1 ? prv2 : prv1);
     }
+    if (has & (cd.n >= 3)) store_piece(out, slot + 2, fc, cd.x2, ib, fdi, fprv);
     wave_sync();
     /* a candidate that extends the previous piece only moves that piece's right end; of
      * the members of a run only the last one (in this chunk) writes, after the heads. */
     {
-      unsigned long long m_head0 = ballot(has && head0);
-      if (has && !head0) {
-        unsigned long long above = m_has & ~lb & ~(1ull << lane);
-        bool next_is_head = true;
-        if (above) next_is_head = ((m_head0 >> ctz64(above)) & 1ull) != 0;
-        if (cd.n >= 2 || next_is_head) out.mx(slot) = hi0;
-      }
+      const unsigned long long m_head0 = ballot(has & head0);
+      const unsigned long long above = m_has & ~lb & ~(1ull << lane);
+      /* (bit 63 keeps ctz64 defined for the top lane of the run; it never is the lowest bit
+       * of a non-empty `above`) */
+      const bool next_is_head = !above | (((m_head0 >> ctz64(above | (1ull << 63))) & 1ull) != 0);
+      if (has & !head0 & ((cd.n >= 2) | next_is_head)) out.mx(slot) = hi0;
     }
     wave_sync();
     n_out += heads_total;

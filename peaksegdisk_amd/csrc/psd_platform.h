@@ -112,7 +112,11 @@ PSD_D double rdlane_d(double v, int src) {
 #ifdef PSD_EMU
 PSD_D long long cycle_now() { return 0; }
 #else
-PSD_D long long cycle_now() { return (long long)__builtin_readcyclecounter(); }
+/* (nodebug: in a build with line tables the counter read carries the line of the stamp that
+ * uses it, which is how tools/isa_counts.py --phases finds the stamps in the ISA) */
+PSD_D __attribute__((nodebug)) long long cycle_now() {
+  return (long long)__builtin_readcyclecounter();
+}
 #endif
 
 /* flag hand-off between two waves of a workgroup through LDS */

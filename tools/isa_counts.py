@@ -10,7 +10,14 @@ Compiles peakseg_hip.cpp for the device only (-S), takes psd::lat::fpop_forward_
     (get_larger_root: a log and two divisions per trip; get_smaller_root: an exp and one), with
     their instruction counts per trip.
 
-usage: python tools/isa_counts.py [out.txt]   (no GPU needed)
+With --phases the stamped diagnostic build (-DPSD_PROFILE, line tables on) is compiled as well
+and its per-data-point code is split at the cycle stamps (PSD_PROF_T0 / PSD_PROF_ADD /
+PSD_PROF_SUB in the sources): per phase, the static number of branches, of exec-mask regions
+(s_*_saveexec), of s_cbranch_execz skips, of s_waitcnt and of SALU / VALU instructions, counted
+in layout order between two stamps (the fall-through path and the blocks the compiler laid out
+inside it; out-of-line cold blocks are listed under the phase whose stamp follows them).
+
+usage: python tools/isa_counts.py [--phases] [out.txt]   (no GPU needed)
 """
 import os
 import re
@@ -25,7 +32,74 @@ import __graft_entry__ as entry  # noqa: E402
 KERNEL = "_ZN3psd3lat19fpop_forward_kernelENS_10DeviceArgsE"
 
 
+def stamp_sites(csrc):
+    """{(file name, line): label} of every cycle stamp in the kernel sources."""
+    sites = {}
+    for name in os.listdir(csrc):
+        for no, ln in enumerate(open(os.path.join(csrc, name), errors="replace"), 1):
+            m = re.search(r"\bPSD_PROF_(T0|SUB0|ADD|SUB)\((\w*)\)", ln)
+            if m and not ln.lstrip().startswith("#define"):
+                sites[(name, no)] = m.group(2) if m.group(1) in ("ADD", "SUB") else "(start)"
+    return sites
+
+
+def phase_table(csrc, work):
+    """Static counts per phase of the stamped build, split at the cycle-counter reads."""
+    asm = os.path.join(work, "prof.s")
+    flags = [f for f in entry.HIP_FLAGS if f not in ("-shared", "-fPIC")]
+    subprocess.run([entry.HIPCC] + flags + ["--cuda-device-only", "-S", "-DPSD_PROFILE",
+                    "-gline-tables-only", "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
+                    os.path.join(csrc, "peakseg_hip.cpp"), "-o", asm], check=True,
+                   stderr=subprocess.DEVNULL)
+    text = open(asm).read()
+    files = {int(m.group(1)): os.path.basename(m.group(3) or m.group(2)) for m in
+             re.finditer(r'\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', text)}
+    start = text.index("\n" + KERNEL + ":")
+    body = text[start:text.index(".end_amdhsa_kernel", start)]
+    sites = stamp_sites(csrc)
+    keys = ("branches", "execz skips", "exec regions", "s_waitcnt", "SALU", "VALU", "LDS", "all")
+    order, table = [], {}
+    pending = dict.fromkeys(keys, 0)
+    loc = None
+    for ln in body.splitlines():
+        t = ln.strip()
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
+        if m:
+            loc = (files.get(int(m.group(1)), "?"), int(m.group(2)))
+            continue
+        i = t.split(";")[0].strip()
+        if not i or i.startswith(".") or i.endswith(":"):
+            continue
+        if i.startswith(("s_memtime", "s_memrealtime")) and loc in sites:
+            label = "%s @ %s:%d" % (sites[loc], loc[0], loc[1])
+            if label not in table:
+                order.append(label)
+                table[label] = dict.fromkeys(keys, 0)
+            for k in keys:
+                table[label][k] += pending[k]
+            pending = dict.fromkeys(keys, 0)
+            continue
+        pending["all"] += 1
+        pending["branches"] += i.startswith(("s_cbranch", "s_branch"))
+        pending["execz skips"] += i.startswith("s_cbranch_exec")
+        pending["exec regions"] += "saveexec" in i
+        pending["s_waitcnt"] += i.startswith("s_waitcnt")
+        pending["SALU"] += i.startswith("s_")
+        pending["VALU"] += i.startswith("v_")
+        pending["LDS"] += i.startswith("ds_")
+    out = ["static counts per phase of the stamped build (instructions in layout order up to each "
+           "stamp; '(start)' rows: code between the end of one phase and the start of the next):",
+           "  %-46s" % "stamp" + "".join("%13s" % k for k in keys)]
+    for label in order:
+        out.append("  %-46s" % label + "".join("%13d" % table[label][k] for k in keys))
+    out.append("  %-46s" % "(after the last stamp)" + "".join("%13d" % pending[k] for k in keys))
+    return out
+
+
 def main():
+    phases = "--phases" in sys.argv
+    if phases:
+        sys.argv.remove("--phases")
     csrc = os.path.join(ROOT, "peaksegdisk_amd", "csrc")
     work = tempfile.mkdtemp(prefix="psd_isa_")
     asm = os.path.join(work, "dev.s")
@@ -61,6 +135,8 @@ def main():
         ("  v_accvgpr_read / write (VGPR spills to AGPRs)", lambda i: i.startswith("v_accvgpr")),
         ("SALU (s_*)", lambda i: i.startswith("s_")),
         ("  branches", lambda i: i.startswith(("s_cbranch", "s_branch"))),
+        ("    s_cbranch_execz / execnz", lambda i: i.startswith("s_cbranch_exec")),
+        ("  exec-mask regions (s_*_saveexec)", lambda i: "saveexec" in i),
         ("  s_waitcnt", lambda i: i.startswith("s_waitcnt")),
         ("  calls (s_swappc)", lambda i: i.startswith("s_swappc")),
         ("LDS reads (ds_read*)", lambda i: i.startswith("ds_read")),
@@ -98,6 +174,8 @@ def main():
         out.append("  %-12s %-36s %3d instructions per trip: %d VALU, %d SALU, %d LDS" % (
             name, kind, len(block), sum(1 for i in block if i.startswith("v_")),
             sum(1 for i in block if i.startswith("s_")), n_lds))
+    if phases:
+        out += phase_table(csrc, work)
     text_out = "\n".join(out) + "\n"
     sys.stdout.write(text_out)
     if len(sys.argv) > 1:

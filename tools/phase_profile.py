@@ -4,6 +4,10 @@ phases of the forward kernel) into gpurun_out/, run a small grid and print, per 
 of cycles spent in each phase.  Shares only -- a stamped build is slower than the real one.
 
 usage (on the GPU box): python tools/phase_profile.py [bins] [penalties]
+PSD_PROFILE_LIB=<lib.so> takes a stamped library built beforehand (tools/build_variant.sh <tree>
+<lib.so> -DPSD_PROFILE) instead of compiling this tree; PSD_PROFILE_PENALTIES=a,b,... prints only
+the problems whose penalty starts with one of the given strings, with cycles per data point and
+phase instead of shares.
 """
 import ctypes
 import os
@@ -32,10 +36,13 @@ def main():
     lib_path = os.path.join(out, "libpeaksegdisk_hip_prof.so")
     csrc = os.path.join(ROOT, "peaksegdisk_amd", "csrc")
     import __graft_entry__ as entry
-    subprocess.run([entry.HIPCC] + entry.HIP_FLAGS + ["-DPSD_PROFILE"]
-                   + os.environ.get("PSD_PROFILE_FLAGS", "").split() + [
-                    "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
-                    os.path.join(csrc, "peakseg_hip.cpp"), "-o", lib_path], check=True)
+    if os.environ.get("PSD_PROFILE_LIB"):  # a stamped library built beforehand (A/B of two trees)
+        lib_path = os.path.abspath(os.environ["PSD_PROFILE_LIB"])
+    else:
+        subprocess.run([entry.HIPCC] + entry.HIP_FLAGS + ["-DPSD_PROFILE"]
+                       + os.environ.get("PSD_PROFILE_FLAGS", "").split() + [
+                        "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
+                        os.path.join(csrc, "peakseg_hip.cpp"), "-o", lib_path], check=True)
     from peaksegdisk_amd import _native, synthetic
     from peaksegdisk_amd.grid import ProblemSet
     lib = _native.declare(ctypes.CDLL(lib_path))
@@ -50,7 +57,10 @@ def main():
     f_ms, b_ms = pset.solve()
     print("bins=%d penalties=%d forward=%.1f ms backtrack=%.1f ms (stamped build)" % (
         bins, npen, f_ms, b_ms))
+    only = [x for x in os.environ.get("PSD_PROFILE_PENALTIES", "").split(",") if x]
     for p in range(npen):
+        if only and not any(str(pens[p]).startswith(x) for x in only):
+            continue
         buf = np.zeros(2 * NP, dtype=np.int64)
         if lib.peakseg_hip_problem_set_profile(pset._h, p, buf.ctypes.data) < 0:
             raise SystemExit("profile not available")
@@ -58,8 +68,12 @@ def main():
         for w in range(2):
             v = buf[w * NP:(w + 1) * NP]
             tot = float(v[9])
-            shares = " ".join("%s=%.1f%%" % (NAMES[i].split("(")[0], 100.0 * v[i] / tot)
-                              for i in list(range(9)) + list(range(10, 16)) + [20, 21, 22])
+            if only:  # cycles per data point
+                shares = " ".join("%s=%.0f" % (NAMES[i].split("(")[0], v[i] / bins)
+                                  for i in list(range(9)) + list(range(10, 16)) + [20, 21, 22])
+            else:
+                shares = " ".join("%s=%.1f%%" % (NAMES[i].split("(")[0], 100.0 * v[i] / tot)
+                                  for i in list(range(9)) + list(range(10, 16)) + [20, 21, 22])
             shares += " | wave-level Newton trips per step: spec=%.1f small=%.1f large=%.1f walk rounds=%.1f" % (
                 v[16] / bins, v[17] / bins, v[18] / bins, v[19] / bins)
             print("pen=%-18s wave%d cyc/step=%7.0f mean_int=%.2f | %s" % (
