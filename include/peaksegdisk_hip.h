@@ -39,8 +39,9 @@ extern "C" {
  *                               per GPU sets it from its rank
  * PEAKSEG_HIP_DEVICES=all|0,1,..  fan-out inside one process (takes precedence over
  *                               PEAKSEG_HIP_DEVICE): PeakSegFPOP_disk_batch, PeakSegFPOP_dir_batch
- *                               and PeakSegFPOP_sequential_search_batch deal their dynamic programs
- *                               (the search batch: its directories) to one shard per listed device,
+ *                               and the search batches (PeakSegFPOP_sequential_search_batch,
+ *                               PeakSegFPOP_parallel_search_batch) deal their dynamic programs
+ *                               (the search batches: their directories) to one shard per listed device,
  *                               longest predicted first, and solve each shard in a problem set of its
  *                               own on a host thread of its own; an id listed twice gets two sets,
  *                               one after the other.  PeakSegFPOP_disk and
@@ -138,6 +139,40 @@ int PeakSegFPOP_sequential_search(const char *problem_dir, int peaks_int, int ve
 int PeakSegFPOP_sequential_search_batch(int n_dirs, char **problem_dirs, const int *peaks_int,
                                         int verbose, int row_capacity, psd_search_row *rows,
                                         int *n_rows, int *chosen_row, int *status_out);
+
+/* A penalty search that asks for `width` models per round instead of one (additive; the
+ * sequential entries above keep the reference's exact penalty sequence).  Round 1 is the
+ * reference's: penalties "0" and "Inf" and the max.peaks check.  Every later round requests,
+ * first, the reference's secant penalty of the bracket (under, over) at its start and, after it,
+ * up to width-1 penalties strictly inside the bracket, placed by a pure function of the bracket
+ * rows, the target and width; all of a round's models are computed in ONE
+ * PeakSegFPOP_dir_batch call, which deals them over PEAKSEG_HIP_DEVICES when that is set.  The
+ * secant model decides as the reference's one model does (peaks equal to a bracket end's: no
+ * model lies between, the search ends with `under`); otherwise every model of the round may
+ * narrow the bracket, and a model with exactly peaks_int peaks ends the search (the one with the
+ * largest penalty if several have).  The chosen model never has more peaks than asked.  Every row
+ * leaves the reference's three files and consistent files are reused (cached = 1).  rows: the
+ * models in the order requested, `iteration` = the round, under_peaks / over_peaks = the bracket
+ * at the round's start.  width: 1 = the sequence of PeakSegFPOP_sequential_search, 0 = the
+ * default (8), at most 256.  A round whose launch reports ERROR_DEVICE_MEMORY is repeated for
+ * its missing models at half the width, which the rest of the search keeps.
+ * peakseg_hip_last_fanout* describe the last round's PeakSegFPOP_dir_batch.
+ * Status: 0, a solver status, ERROR_SEARCH_TOO_MANY_PEAKS or ERROR_SEARCH_ARGUMENTS. */
+int PeakSegFPOP_parallel_search(const char *problem_dir, int peaks_int, int width, int verbose,
+                                int row_capacity, psd_search_row *rows, int *n_rows,
+                                int *chosen_row);
+
+/* The parallel search over several problem directories in lockstep: all models every active
+ * directory wants in a round go into one PeakSegFPOP_dir_batch call, and each directory ends
+ * with the rows and files of PeakSegFPOP_parallel_search on that directory alone.  Arrays as for
+ * PeakSegFPOP_sequential_search_batch; a directory listed twice is refused, a failing directory
+ * keeps its status and the others go on.  Under PEAKSEG_HIP_DEVICES the directories are dealt
+ * to one shard per listed device, as the sequential batch deals them.  Returns the first
+ * non-zero status. */
+int PeakSegFPOP_parallel_search_batch(int n_dirs, char **problem_dirs, const int *peaks_int,
+                                      int width, int verbose, int row_capacity,
+                                      psd_search_row *rows, int *n_rows, int *chosen_row,
+                                      int *status_out);
 
 /* The text the reference's glue passes to Rf_error for a status
  * (/root/reference/src/interface.cpp:16-55); returns buf; empty string for status 0. */

@@ -110,6 +110,14 @@ def declare(lib):
         c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_int), c.c_int, c.c_int,
         c.POINTER(PsdSearchRow), c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int)]
     lib.PeakSegFPOP_sequential_search_batch.restype = c.c_int
+    lib.PeakSegFPOP_parallel_search.argtypes = [
+        c.c_char_p, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(PsdSearchRow),
+        c.POINTER(c.c_int), c.POINTER(c.c_int)]
+    lib.PeakSegFPOP_parallel_search.restype = c.c_int
+    lib.PeakSegFPOP_parallel_search_batch.argtypes = [
+        c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_int), c.c_int, c.c_int, c.c_int,
+        c.POINTER(PsdSearchRow), c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int)]
+    lib.PeakSegFPOP_parallel_search_batch.restype = c.c_int
     lib.peakseg_hip_problem_set_set_penalty.argtypes = [c.c_void_p, c.c_int, c.c_double]
     lib.peakseg_hip_problem_set_set_penalty.restype = c.c_int
     lib.peakseg_hip_problem_set_arena_bytes_used.argtypes = [c.c_void_p]
@@ -170,6 +178,7 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_packed_download", "peakseg_hip_problem_set_cycles",
     "peakseg_hip_measured_rates", "peakseg_hip_spin_limit", "peakseg_hip_problem_set_max_spin",
     "peakseg_hip_last_fanout", "peakseg_hip_last_fanout_entries",
+    "PeakSegFPOP_parallel_search", "PeakSegFPOP_parallel_search_batch",
 ]
 
 if not os.path.exists(LIB_PATH):

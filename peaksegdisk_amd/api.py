@@ -460,3 +460,97 @@ def sequentialSearch_dir_batch(problem_dirs, peaks_int, verbose=0, devices=None)
         out.append(_search_result(problem_dirs[d],
                                   [rows[d * cap + k] for k in range(n_rows[d])], chosen[d]))
     return out
+
+
+# ---- the parallel penalty search (additive) ----------------------------
+
+def _check_width(width):
+    if width is None:
+        return 0
+    if not (isinstance(width, (int, np.integer)) and not isinstance(width, bool)
+            and 0 <= width <= 256):
+        raise ValueError("width: None, or an integer from 0 (the default width) to 256")
+    return int(width)
+
+
+def parallelSearch_dir(problem_dir, peaks_int, width=None, verbose=0, devices=None):
+    """The model with peaks_int peaks (or the next simpler one, as sequentialSearch_dir), found
+    with `width` models per round instead of one: every round asks for the reference's secant
+    penalty and up to width-1 more inside the bracket, all solved in one launch
+    (PeakSegFPOP_parallel_search), so the search takes about a third to a half of the dependent
+    rounds.  width=None: the library's default; width=1: sequentialSearch_dir's own sequence.
+    devices: "all" or device ids -- each round's models dealt over the listed devices
+    (PEAKSEG_HIP_DEVICES for this call; None: the environment decides).  Same result shape as
+    sequentialSearch_dir: $others has one row per model, `iteration` is the round."""
+    import ctypes
+    if not (isinstance(peaks_int, (int, np.integer)) and not isinstance(peaks_int, bool)
+            and 0 <= peaks_int):
+        raise ValueError("is.integer(peaks.int) && length(peaks.int) == 1 && 0 <= peaks.int "
+                         "is not TRUE")
+    if not isinstance(problem_dir, str):
+        raise ValueError("is.character(problem.dir) is not TRUE")
+    width = _check_width(width)
+    cap = 1024
+    rows = (_native.PsdSearchRow * cap)()
+    n_rows = ctypes.c_int(0)
+    chosen = ctypes.c_int(-1)
+    with _devices_knob(devices):
+        st = _native.lib.PeakSegFPOP_parallel_search(
+            os.fsencode(problem_dir), int(peaks_int), width, int(bool(verbose)), cap, rows,
+            ctypes.byref(n_rows), ctypes.byref(chosen))
+    if st == _native.ERROR_SEARCH_TOO_MANY_PEAKS:
+        raise ValueError(_native.last_error())
+    if st != 0:
+        bg = os.path.realpath(os.path.join(problem_dir, "coverage.bedGraph"))
+        pen = rows[n_rows.value].penalty_str.decode() if n_rows.value < cap else ""
+        msg = _native.status_message(st, bg, pen, "%s_penalty=%s.db" % (bg, pen))
+        detail = _native.last_error()
+        if st >= _native.ERROR_NO_HIP_DEVICE and detail:
+            msg = "%s (%s)" % (msg, detail)
+        raise PeakSegError(st, msg)
+    return _search_result(problem_dir, [rows[k] for k in range(n_rows.value)], chosen.value)
+
+
+def parallelSearch_dir_batch(problem_dirs, peaks_int, width=None, verbose=0, devices=None):
+    """parallelSearch_dir over several problem directories in lockstep: each directory gets the
+    result parallelSearch_dir(dir, peaks, width) gives, and all the models the searches ask for
+    in a round are computed in one launch (PeakSegFPOP_parallel_search_batch).  peaks_int: one
+    target for all, or one per directory.  devices: "all" or device ids -- the directories dealt
+    to one shard per listed device.  Returns the list of results; a failed search raises for the
+    first failure."""
+    import ctypes
+    problem_dirs = list(problem_dirs)
+    n = len(problem_dirs)
+    if isinstance(peaks_int, (int, np.integer)) and not isinstance(peaks_int, bool):
+        peaks_int = [int(peaks_int)] * n
+    peaks_int = [int(p) for p in peaks_int]
+    if len(peaks_int) != n or any(p < 0 for p in peaks_int):
+        raise ValueError("peaks.int: one non-negative integer, or one per problem directory")
+    if not all(isinstance(d, str) for d in problem_dirs):
+        raise ValueError("is.character(problem.dir) is not TRUE")
+    width = _check_width(width)
+    if n == 0:
+        return []
+    cap = 1024
+    rows = (_native.PsdSearchRow * (cap * n))()
+    dirs = (ctypes.c_char_p * n)(*[os.fsencode(d) for d in problem_dirs])
+    peaks = (ctypes.c_int * n)(*peaks_int)
+    n_rows = (ctypes.c_int * n)()
+    chosen = (ctypes.c_int * n)()
+    status = (ctypes.c_int * n)()
+    with _devices_knob(devices):
+        _native.lib.PeakSegFPOP_parallel_search_batch(n, dirs, peaks, width, int(bool(verbose)),
+                                                      cap, rows, n_rows, chosen, status)
+    out = []
+    for d in range(n):
+        if status[d] == _native.ERROR_SEARCH_TOO_MANY_PEAKS:
+            raise ValueError(_native.last_error())
+        if status[d] != 0:
+            bg = os.path.realpath(os.path.join(problem_dirs[d], "coverage.bedGraph"))
+            k = n_rows[d]
+            pen = rows[d * cap + k].penalty_str.decode() if k < cap else ""
+            raise PeakSegError(status[d], _native.status_message(
+                status[d], bg, pen, "%s_penalty=%s.db" % (bg, pen)))
+        out.append(_search_result(problem_dirs[d],
+                                  [rows[d * cap + k] for k in range(n_rows[d])], chosen[d]))
+    return out

@@ -106,3 +106,74 @@ sequentialSearch_dir_batch <- function
     out
   })
 }
+
+search_models <- function
+### the value of a penalty search from the rows a native search returned: the chosen model with
+### $others, every model read back with PeakSegFPOP_dir (cache hits)
+(problem.dir, penalty, iteration, under, over, chosen){
+  model.list <- lapply(seq_along(penalty), function(i){
+    L <- PeakSegFPOP_dir(problem.dir, penalty[i])
+    L$loss$iteration <- iteration[i]
+    L$loss$under <- under[i]
+    L$loss$over <- over[i]
+    L
+  })
+  out <- model.list[[chosen]]
+  out$others <- do.call(rbind, lapply(model.list, "[[", "loss"))[order(iteration)]
+  out
+}
+
+parallelSearch_dir <- function
+### The model with peaks.int peaks (or the next simpler one, as sequentialSearch_dir) found with
+### width models per round instead of one: each round asks for the secant penalty of
+### sequentialSearch_dir and up to width-1 more inside the bracket, all solved in one launch.
+### width=0L: the library's default; width=1L: the penalties of sequentialSearch_dir.  devices:
+### "all" or GPU ids, each round's models dealt over the listed GPUs.
+(problem.dir, peaks.int, width=0L, verbose=0, devices=NULL){
+  stopifnot(is.integer(peaks.int) && length(peaks.int)==1 && 0 <= peaks.int)
+  stopifnot(is.character(problem.dir) && length(problem.dir)==1)
+  stopifnot(is.integer(width) && length(width)==1 && 0 <= width && width <= 256)
+  saved <- set_devices_knob(devices)
+  on.exit(restore_devices_knob(saved), add=TRUE)
+  capacity <- 1024L
+  res <- .C(
+    "PeakSegFPOP_parallel_search_interface",
+    problem.dir, peaks.int, width, as.integer(verbose), capacity,
+    penalty=rep(strrep(" ", 39), capacity), iteration=integer(capacity),
+    under=integer(capacity), over=integer(capacity),
+    n=integer(1), chosen=integer(1),
+    PACKAGE="PeakSegDisk")
+  i.vec <- seq_len(res$n)
+  search_models(problem.dir, res$penalty[i.vec], res$iteration[i.vec], res$under[i.vec],
+                res$over[i.vec], res$chosen)
+}
+
+parallelSearch_dir_batch <- function
+### parallelSearch_dir on several problem directories in lockstep: every directory gets the
+### result parallelSearch_dir(problem.dir, peaks.int, width) gives, and all models the searches
+### ask for in a round are computed in one launch.  devices: "all" or GPU ids, the directories
+### dealt to one shard per listed GPU.
+(problem.dir.vec, peaks.int.vec, width=0L, verbose=0, devices=NULL){
+  stopifnot(is.character(problem.dir.vec), is.integer(peaks.int.vec), all(0 <= peaks.int.vec))
+  stopifnot(is.integer(width) && length(width)==1 && 0 <= width && width <= 256)
+  n <- length(problem.dir.vec)
+  saved <- set_devices_knob(devices)
+  on.exit(restore_devices_knob(saved), add=TRUE)
+  peaks.int.vec <- rep(peaks.int.vec, l=n)
+  capacity <- 1024L
+  res <- .C(
+    "PeakSegFPOP_parallel_search_batch_interface",
+    problem.dir.vec, as.integer(n), peaks.int.vec, width, as.integer(verbose), capacity,
+    penalty=rep(strrep(" ", 39), capacity*n), iteration=integer(capacity*n),
+    under=integer(capacity*n), over=integer(capacity*n),
+    n.models=integer(n), chosen=integer(n), status=integer(n),
+    PACKAGE="PeakSegDisk")
+  if(any(res$status != 0)){
+    stop("error code ", res$status[res$status != 0][1])
+  }
+  lapply(seq_len(n), function(d){
+    i.vec <- (d-1L)*capacity + seq_len(res$n.models[d])
+    search_models(problem.dir.vec[d], res$penalty[i.vec], res$iteration[i.vec], res$under[i.vec],
+                  res$over[i.vec], res$chosen[d])
+  })
+}
