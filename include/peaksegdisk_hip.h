@@ -33,6 +33,9 @@ extern "C" {
 #define ERROR_SEARCH_ARGUMENTS 15  /* PeakSegFPOP_sequential_search: bad arguments / row capacity */
 #define ERROR_SEARCH_TOO_MANY_PEAKS 16 /* peaks.int exceeds the maximum for the data; the text of
                                           R/sequentialSearch_dir.R:57-66 is in peakseg_hip_last_error() */
+#define ERROR_DENSE_ARGUMENTS 17   /* dense counts that cannot be solved: 2^31 or more bases, a
+                                      negative count, counts that sum to 2^53 or more, 2^30 or more
+                                      runs; the contig and the reason are in peakseg_hip_last_error() */
 
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
@@ -74,7 +77,8 @@ extern "C" {
  * PEAKSEG_HIP_RATES=lat,thr     diagnostic: data points per second per problem the launch planner
  *                               assumes for the latency / throughput build (default: measured by
  *                               this process's earlier solves, else 96000,58000)
- * PEAKSEG_HIP_TIMING=1          phase timings of the file-level calls on stderr */
+ * PEAKSEG_HIP_TIMING=1          phase timings of the file-level calls and of the creation of a
+ *                               problem set (the dense encoder's launches included) on stderr */
 
 /* ---- the reference's boundary -------------------------------------------------------- */
 
@@ -237,6 +241,31 @@ int peakseg_hip_problem_set_create(int device, int n_contigs, const int *contig_
                                    const int *problem_contig, const double *problem_penalty,
                                    unsigned long long arena_pieces, psd_problem_set **out);
 
+/* The same set from DENSE coverage: contig c is contig_n_bases[c] int32 counts, one per base, and
+ * the run-length encoding happens on the device (three launches per call however many contigs it
+ * has; a run starts at a contig's first base and wherever a count differs from the one before
+ * it).  counts_on_device = 0: contig_counts[] are host arrays, uploaded and freed again after the
+ * encoding; 1: they are device addresses (multiples of 4) on `device`, read in place -- by
+ * launches on the null stream, so after everything the caller has queued there -- and not
+ * referred to after the call returns.  From there on the set is one of
+ * peakseg_hip_problem_set_create: contig_n_bins = the runs, count = the run's count, weight = its
+ * length; every call below works on it.  In addition it keeps run_end[] (offset of each run's last
+ * base + 1 from the contig's first base), which peakseg_hip_problem_set_pack_segments needs, and
+ * it knows its trivial models (penalty +Inf, or a contig whose counts are all equal: the
+ * reference's one-segment branch, PeakSegFPOPLog.cpp:224-243): solve launches only the other
+ * problems, and result / segments / pack_tables / pack_segments / loss serve the closed form.
+ * Checks, in this order: penalties (NaN: ERROR_PENALTY_NOT_FINITE, negative:
+ * ERROR_PENALTY_NEGATIVE, +Inf is allowed); a contig without bases: ERROR_NO_DATA, with 2^31 or
+ * more: ERROR_DENSE_ARGUMENTS; the device: ERROR_NO_HIP_DEVICE (there is no host encoder); what
+ * the encoder finds -- a negative count, counts that sum to 2^53 or more (the reference's double
+ * accumulation would round), 2^30 or more runs in a contig: ERROR_DENSE_ARGUMENTS. */
+int peakseg_hip_problem_set_create_dense(int device, int n_contigs,
+                                         const long long *contig_n_bases,
+                                         const int *const *contig_counts, int counts_on_device,
+                                         int n_problems, const int *problem_contig,
+                                         const double *problem_penalty,
+                                         unsigned long long arena_pieces, psd_problem_set **out);
+
 /* Run forward DP + backtrack for every problem of the set; inputs are already resident.
  * *forward_ms = duration of the kernel, measured with HIP events on the stream it runs on.
  * Each workgroup decodes its segmentation right after its last data point, inside the same
@@ -309,6 +338,24 @@ long long peakseg_hip_problem_set_pack_tables(psd_problem_set *set, long long *r
                                               const int **start_dev, const double **mean_dev);
 int peakseg_hip_problem_set_packed_download(psd_problem_set *set, int *start_out, double *mean_out);
 
+/* The reference's segments table of every problem of a solved set made from dense counts, packed
+ * IN HBM like pack_tables (one launch, a workgroup per problem): row r of a problem has
+ * chromStart = seg_start < 0 ? first : first + run_end[seg_start], chromEnd = the row before's
+ * chromStart (row 0: first + the contig's bases) and its mean; its status is its parity (even:
+ * background, odd: peak).  first_chromStart: one per CONTIG, NULL = zeros.  Returns the total
+ * number of rows, -1 on failure (a set that was not made from dense counts has no run_end[]).
+ * The device addresses stay valid until the set is solved again or destroyed. */
+long long peakseg_hip_problem_set_pack_segments(psd_problem_set *set, const int *first_chromStart,
+                                                long long *rows_out, const int **chromStart_dev,
+                                                const int **chromEnd_dev, const double **mean_dev);
+int peakseg_hip_problem_set_packed_segments_download(psd_problem_set *set, int *chromStart_out,
+                                                     int *chromEnd_out, double *mean_out);
+
+/* The ten fields of the reference's loss.tsv row of one solved problem, in its order and with its
+ * arithmetic: penalty, segments, peaks, bases, bedGraph.lines, mean.pen.cost, total.loss,
+ * equality.constraints, mean.intervals, max.intervals.  0 or -1. */
+int peakseg_hip_problem_set_loss(psd_problem_set *set, int problem, double *out);
+
 /* Shader cycles a problem's workgroup ran in the last launch that worked on it (0 when
  * unknown); with the device's clock, data points / cycles is the problem's rate: the dealing of
  * problems to ranks is sized from it. */
@@ -333,6 +380,19 @@ void peakseg_hip_problem_set_destroy(psd_problem_set *set);
  * number of data lines and a hash of everything parsed. */
 int peakseg_hip_parse_probe(const char *path, int use_fast, int *n_lines,
                             unsigned long long *hash);
+
+/* Tests: the dense encoder alone.  Arguments as peakseg_hip_problem_set_create_dense; per contig
+ * runs_out / min_out / max_out / sum_out, and the concatenated count / weight / run_end arrays
+ * (any may be NULL).  Statuses as the creator's, without the penalties. */
+int peakseg_hip_dense_encode_probe(int device, int n_contigs, const long long *n_bases,
+                                   const int *const *counts, int counts_on_device,
+                                   long long *runs_out, int *count_out, int *weight_out,
+                                   int *run_end_out, int *min_out, int *max_out,
+                                   long long *sum_out);
+/* the encoder's tile: bases one workgroup encodes (tests aim at its boundaries) */
+int peakseg_hip_dense_tile_bases(void);
+/* milliseconds (HIP events) of the three launches of the calling thread's last encoding */
+int peakseg_hip_dense_last_encode_ms(float *count_ms, float *scan_ms, float *scatter_ms);
 
 /* Tests: R's paste() of a double (15 significant digits) as the penalty search and the timing
  * files format numbers; returns the length. */

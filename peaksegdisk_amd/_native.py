@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libpeaksegdisk_hip.so")
 ERROR_NO_HIP_DEVICE = 12
 ERROR_DEVICE_SOLVER = 13
 ERROR_DEVICE_MEMORY = 14
+ERROR_DENSE_ARGUMENTS = 17
 
 
 class PsdResult(ctypes.Structure):
@@ -157,6 +158,29 @@ def declare(lib):
     lib.peakseg_hip_last_fanout.restype = c.c_int
     lib.peakseg_hip_last_fanout_entries.argtypes = [c.c_int, c.POINTER(c.c_int)]
     lib.peakseg_hip_last_fanout_entries.restype = c.c_int
+    lib.peakseg_hip_problem_set_create_dense.argtypes = [
+        c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.c_int,
+        c.c_int, c.POINTER(c.c_int), c.POINTER(c.c_double), c.c_ulonglong,
+        c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_create_dense.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_segments.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_pack_segments.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_segments_download.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_problem_set_packed_segments_download.restype = c.c_int
+    lib.peakseg_hip_problem_set_loss.argtypes = [c.c_void_p, c.c_int, c.POINTER(c.c_double)]
+    lib.peakseg_hip_problem_set_loss.restype = c.c_int
+    lib.peakseg_hip_dense_encode_probe.argtypes = [
+        c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.c_int,
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_dense_encode_probe.restype = c.c_int
+    lib.peakseg_hip_dense_tile_bases.argtypes = []
+    lib.peakseg_hip_dense_tile_bases.restype = c.c_int
+    lib.peakseg_hip_dense_last_encode_ms.argtypes = [
+        c.POINTER(c.c_float), c.POINTER(c.c_float), c.POINTER(c.c_float)]
+    lib.peakseg_hip_dense_last_encode_ms.restype = c.c_int
     return lib
 
 
@@ -179,6 +203,10 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_measured_rates", "peakseg_hip_spin_limit", "peakseg_hip_problem_set_max_spin",
     "peakseg_hip_last_fanout", "peakseg_hip_last_fanout_entries",
     "PeakSegFPOP_parallel_search", "PeakSegFPOP_parallel_search_batch",
+    "peakseg_hip_problem_set_create_dense", "peakseg_hip_problem_set_pack_segments",
+    "peakseg_hip_problem_set_packed_segments_download", "peakseg_hip_problem_set_loss",
+    "peakseg_hip_dense_encode_probe", "peakseg_hip_dense_tile_bases",
+    "peakseg_hip_dense_last_encode_ms",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -307,6 +307,113 @@ def PeakSegFPOP_vec(count_vec, pen_num):
     return PeakSegFPOP_df(coverage_df, pen_num)
 
 
+# ---- dense coverage in memory (additive: no file anywhere) ----------------------------------
+
+def _read_text_table(text, names):
+    """_read_table of what the solver would have written, without the file"""
+    import io
+    return pd.read_csv(io.StringIO(text), sep="\t", header=None, names=names, na_filter=False,
+                       float_precision="round_trip")
+
+
+def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=None, device=0):
+    """PeakSegFPOP_vec without its files: dense integer coverage (one count per base) is
+    run-length encoded and solved on the GPU, and the reference's result comes back as data
+    frames.  count_vecs: one vector or a list of them (int32 numpy arrays or torch tensors are
+    passed as they are -- a tensor on cuda:`device` is never copied --, other integer arrays
+    are converted); penalties: one list for all vectors or one list per vector; chrom_starts:
+    the coordinate of each vector's first base (default 0).  Returns, for a single vector, a
+    list over its penalties, else a list over vectors of such lists, of PeakSegFPOP_dir_result
+    whose $segments and $loss are what PeakSegFPOP_dir reads from the files the file path
+    writes for the same runs (means pass through the files' "%g", penalties through paste())."""
+    from .grid import ProblemSet
+    single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
+        len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
+    vecs = [count_vecs] if single else list(count_vecs)
+    if len(vecs) == 0:
+        raise ValueError("count.vecs must hold at least one vector")
+    pens = list(penalties) if not isinstance(penalties, (int, float, np.integer, np.floating)) \
+        else [penalties]
+    per_vec = len(pens) > 0 and isinstance(pens[0], (list, tuple, np.ndarray))
+    if per_vec:
+        if len(pens) != len(vecs):
+            raise ValueError("penalties: one list per vector (%d lists, %d vectors)"
+                             % (len(pens), len(vecs)))
+        pens = [list(q) for q in pens]
+    else:
+        pens = [pens] * len(vecs)
+    for q in pens:
+        for pen_num in q:
+            _check_pen_num(pen_num)
+    contigs = []
+    for v in vecs:
+        if not hasattr(v, "data_ptr"):
+            v = np.asarray(v)
+            if not np.issubdtype(v.dtype, np.integer):
+                raise ValueError("count.vec must be integer")
+            if v.dtype != np.int32:
+                if v.size and (v.max() > 2 ** 31 - 1 or v.min() < -2 ** 31):
+                    raise ValueError("count.vec must fit 32-bit integers")
+                v = v.astype(np.int32)
+            v = np.ascontiguousarray(v)
+        contigs.append(v)
+    if chrom_starts is None:
+        chrom_starts = [0] * len(vecs)
+    if len(chrom_starts) != len(vecs):
+        raise ValueError("chrom.starts: one per vector")
+    problems, pen_strs = [], []
+    for c, q in enumerate(pens):
+        for pen_num in q:
+            pen_strs.append(paste(pen_num))
+            problems.append((c, float(pen_strs[-1])))
+    if not problems:
+        return [] if single else [[] for _ in vecs]
+    t0 = time.time()
+    try:
+        pset = ProblemSet.from_dense(contigs, problems, device=device)
+    except RuntimeError as e:
+        status = getattr(e, "status", _native.ERROR_DEVICE_SOLVER)
+        msg = _native.status_message(status, "<dense counts>", "", "")
+        detail = _native.last_error()
+        raise PeakSegError(status, "%s (%s)" % (msg, detail) if detail else msg)
+    try:
+        try:
+            pset.solve()
+        except RuntimeError as e:
+            raise PeakSegError(_native.ERROR_DEVICE_SOLVER, str(e))
+        columns = pset.segment_columns(first_chromStart=chrom_starts)
+        rows = [(pset.loss(p), pset.result(p)) for p in range(len(problems))]
+    finally:
+        pset.close()
+    seconds = (time.time() - t0) / len(problems)
+    flat = []
+    for p, (c, _) in enumerate(problems):
+        start, end, mean = columns[p]
+        status = np.where(np.arange(len(start)) % 2 == 0, "background", "peak")
+        seg_text = "".join("%s\t%d\t%d\t%s\t%g\n" % (chrom, a, b, st, m) for a, b, st, m in zip(
+            start.tolist(), end.tolist(), status.tolist(), mean.tolist()))
+        f, r = rows[p]
+        if f[1] == 1 and f[8] == 0 and f[9] == 0:  # the one-segment model's row (drv:224-243)
+            loss_text = "%s\t%d\t%d\t%d\t%d\t%.20g\t%.20g\t%d\t%d\t%d\n" % (
+                pen_strs[p], 1, 0, int(f[3]), int(f[4]), f[5], f[6], 0, 0, 0)
+            megabytes = 0.0
+        else:
+            loss_text = "%.20g\t%d\t%d\t%d\t%d\t%.20g\t%.20g\t%d\t%.20g\t%.20g\n" % (
+                f[0], int(f[1]), int(f[2]), int(f[3]), int(f[4]), f[5], f[6], int(f[7]), f[8], f[9])
+            n = int(f[4])  # the size of the reference's cost-function database
+            megabytes = (32 * n + 12 * (2 * n - 1) + 20 * int(r.total_intervals)) / 1024 / 1024
+        loss = _read_text_table(loss_text, col_name_list["loss"])
+        loss["megabytes"] = float(megabytes)
+        loss["seconds"] = float(seconds)
+        flat.append(PeakSegFPOP_dir_result(
+            _read_text_table(seg_text, col_name_list["segments"]), loss))
+    out, o = [], 0
+    for q in pens:
+        out.append(flat[o:o + len(q)])
+        o += len(q)
+    return out[0] if single else out
+
+
 # ---- PeakSegFPOP_dir for a batch (additive; SURVEY.md section 8 f3) --------------------------
 
 class _devices_knob:

@@ -84,6 +84,9 @@
 #undef PSD_CALL_LDS_OPS
 #undef PSD_PARK_ON_LDS_OVERFLOW
 
+/* run-length encoding of dense coverage and the reference's segments table, on the device */
+#include "dense_encode.h"
+
 #include <ctype.h>
 #include <errno.h>
 #include <limits.h>
@@ -420,6 +423,21 @@ struct psd_problem_set {
   long long pack_capacity = 0, pack_total = -1;
   int parks = 0;                          /* problems parked by the last solve's launches */
   unsigned long long park_pool_pieces = 0; /* ... and what they took from the overflow pool */
+  /* what loss.tsv needs of a contig: its bases (the sum of its bins' widths) */
+  std::vector<long long> contig_bases;
+  /* Sets made from dense counts (peakseg_hip_problem_set_create_dense): run_end[] next to count[]
+   * and weight[], the sum of each contig's counts, and which contigs are constant.  Their trivial
+   * models (penalty +Inf, constant contig) are served in closed form and never launched. */
+  bool dense = false;
+  int *d_run_end = nullptr;
+  std::vector<long long> contig_sum;
+  std::vector<char> contig_constant;
+  int *d_order_run = nullptr; /* launch order of a solve that leaves trivial problems out */
+  /* the reference's segments table, packed (peakseg_hip_problem_set_pack_segments) */
+  int *d_segs_start = nullptr, *d_segs_end = nullptr;
+  double *d_segs_mean = nullptr;
+  long long *d_segs_rows = nullptr;
+  long long segs_capacity = 0, segs_total = -1;
   std::vector<void *> allocs;
   unsigned long long bytes = 0;
 };
@@ -1003,6 +1021,33 @@ extern "C" int peakseg_hip_problem_set_set_penalty(psd_problem_set *s, int p, do
   return 0;
 }
 
+namespace {
+
+/* PEAKSEG_HIP_TIMING=1: where the creation of a set spends its time, on stderr */
+struct CreateLaps {
+  bool on = getenv("PEAKSEG_HIP_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point mark = std::chrono::steady_clock::now();
+  void operator()(const char *what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "peakseg_hip timing: create: %-26s %8.3f s\n", what,
+            std::chrono::duration<double>(now - mark).count());
+    mark = now;
+  }
+};
+
+/* What both creators share, from the point where the contigs' data is known: store, tables,
+ * arena, park slots, streams.  The contig data is either host arrays to upload (count, weight) or
+ * arrays the dense encoder left in HBM (s->d.count, s->d.weight already set; count == nullptr).
+ * Destroys the set when it fails. */
+int create_common(psd_problem_set *s, CreateLaps &lap, const std::vector<double> &min_lm,
+                  const std::vector<double> &max_lm, const std::vector<int> *count,
+                  const std::vector<int> *weight, const int *problem_contig,
+                  const double *problem_penalty, unsigned long long arena_pieces,
+                  psd_problem_set **out);
+
+}  // namespace
+
 extern "C" int peakseg_hip_problem_set_create(int device, int n_contigs, const int *contig_n_bins,
                                               const int *const *contig_count,
                                               const int *const *contig_weight, int n_problems,
@@ -1020,16 +1065,7 @@ extern "C" int peakseg_hip_problem_set_create(int device, int n_contigs, const i
     return ERROR_DEVICE_SOLVER;
   }
   HIP_TRY(hipSetDevice(device));
-  /* PEAKSEG_HIP_TIMING=1: where the creation of a set spends its time, on stderr */
-  const bool timing = getenv("PEAKSEG_HIP_TIMING") != nullptr;
-  auto t_mark = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "peakseg_hip timing: create: %-26s %8.3f s\n", what,
-            std::chrono::duration<double>(now - t_mark).count());
-    t_mark = now;
-  };
+  CreateLaps lap;
   psd_problem_set *s = new psd_problem_set();
   s->device = device;
   s->n_contigs = n_contigs;
@@ -1067,9 +1103,22 @@ extern "C" int peakseg_hip_problem_set_create(int device, int n_contigs, const i
     }
     min_lm[c] = mn;
     max_lm[c] = mx;
+    s->contig_bases.push_back(width_sum);
   }
   s->total_bins = off;
   lap("gather contigs, log range");
+  return create_common(s, lap, min_lm, max_lm, &count, &weight, problem_contig, problem_penalty,
+                       arena_pieces, out);
+}
+
+namespace {
+
+int create_common(psd_problem_set *s, CreateLaps &lap, const std::vector<double> &min_lm,
+                  const std::vector<double> &max_lm, const std::vector<int> *count,
+                  const std::vector<int> *weight, const int *problem_contig,
+                  const double *problem_penalty, unsigned long long arena_pieces,
+                  psd_problem_set **out) {
+  const int device = s->device, n_contigs = s->n_contigs, n_problems = s->n_problems;
   long long dp_bins = 0;
   for (int p = 0; p < n_problems; p++) {
     int c = problem_contig[p];
@@ -1156,7 +1205,8 @@ extern "C" int peakseg_hip_problem_set_create(int device, int n_contigs, const i
       (st = dev_upload(s, &d.contig_off, s->contig_off)) ||
       (st = dev_upload(s, &d.contig_min_log_mean, min_lm)) ||
       (st = dev_upload(s, &d.contig_max_log_mean, max_lm)) ||
-      (st = dev_upload(s, &d.count, count)) || (st = dev_upload(s, &d.weight, weight)) ||
+      (count && ((st = dev_upload(s, &d.count, *count)) ||
+                 (st = dev_upload(s, &d.weight, *weight)))) ||
       (st = dev_alloc(s, &d.result, (size_t)n_problems)) ||
       (st = dev_alloc(s, &d.ar_next_chunk, (size_t)1)) ||
       (st = dev_alloc(s, &d.spill_next, (size_t)1)) ||
@@ -1330,6 +1380,8 @@ extern "C" int peakseg_hip_problem_set_create(int device, int n_contigs, const i
   return 0;
 }
 
+}  // namespace
+
 namespace {
 /* While the kernels of a solve run: a second host thread maps arena blocks AHEAD of what the
  * waves have taken (ar_used, a pinned word the waves add to whenever they take chunks), up to
@@ -1390,6 +1442,48 @@ struct LiveGrower {
  * (profiles/r04/thr_rate_long_contigs.log; rounds 2-3 assumed 27 k, the round-2 build's rate),
  * taken a little low: a problem the planner leaves on the throughput build must not end after
  * the longest one on the latency build. */
+namespace {
+
+/* The reference solves these without a dynamic program (drv:224-243): penalty +Inf, or a contig
+ * whose counts are all equal.  Only sets made from dense counts know the second without the
+ * caller's help; the file path takes the same branch before it creates a set. */
+bool trivial_model(const psd_problem_set *s, int p) {
+  if (!s->dense) return false;
+  return s->prob_penalty[(size_t)p] == INFINITY ||
+         s->contig_constant[(size_t)s->prob_contig[(size_t)p]] != 0;
+}
+
+/* best_cost of the one-segment model (write_trivial in peakseg_files.h, drv:225-231) */
+double trivial_best_cost(const psd_problem_set *s, int c) {
+  const double cum_weighted_count = (double)s->contig_sum[(size_t)c];
+  const double cum_weight = (double)s->contig_bases[(size_t)c];
+  if (cum_weighted_count == 0) return 0;
+  return cum_weighted_count * (1 - psd_log(cum_weighted_count) + psd_log(cum_weight));
+}
+
+/* results and one-row segment tables of the set's trivial models (copies, no launch) */
+int serve_trivial_models(psd_problem_set *s) {
+  for (int p = 0; p < s->n_problems; p++) {
+    if (!trivial_model(s, p)) continue;
+    const int c = s->prob_contig[(size_t)p];
+    const double cum_weight = (double)s->contig_bases[(size_t)c];
+    psd::ProbResult r{};
+    r.best_cost = trivial_best_cost(s, c) / cum_weight;
+    r.n_segments = 1;
+    r.step_reached = s->contig_n[(size_t)c];
+    s->results[(size_t)p] = r;
+    const int start = -1;
+    const double mean = (double)s->contig_sum[(size_t)c] / cum_weight;
+    const long long off = s->prob_seg_off[(size_t)p];
+    HIP_TRY(hipMemcpyAsync(s->d.seg_start + off, &start, sizeof start, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d.seg_mean + off, &mean, sizeof mean, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream)); /* (the sources are locals) */
+  }
+  return 0;
+}
+
+}  // namespace
+
 static std::atomic<double> g_lat_rate{96e3}, g_thr_rate{58e3};
 /* a problem on the packed build (a SIMD shared three ways) against one on the throughput build
  * (two ways): 6144 equal problems ran 18.2 % faster six to a CU than four to a CU */
@@ -1404,10 +1498,26 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
                                              float *backtrack_ms) {
   HIP_TRY(hipSetDevice(s->device));
   g_last_warning.clear();
+  /* What is launched: every problem, longest contig first -- but for the trivial models of a set
+   * made from dense counts, which have a closed form (n_run == n_problems for every other set). */
+  std::vector<int> run_order;
+  run_order.reserve(s->order.size());
+  for (int p : s->order)
+    if (!trivial_model(s, p)) run_order.push_back(p);
+  const int n_run = (int)run_order.size();
+  const int *d_order_first = s->d.prob_order; /* the first launch's order, on the device */
+  if (n_run < s->n_problems) {
+    int st = serve_trivial_models(s);
+    if (st) return st;
+    if (n_run > 0)
+      HIP_TRY(hipMemcpyAsync(s->d_order_run, run_order.data(), sizeof(int) * (size_t)n_run,
+                             hipMemcpyHostToDevice, s->stream));
+    d_order_first = s->d_order_run;
+  }
   /* the latency build wants a CU per problem: beyond that, problems would queue behind each
    * other and a build that packs several problems on a CU (throughput: 4, packed: 6) finishes
    * the set sooner.  PEAKSEG_HIP_VARIANT=lat|thr|pk overrides (tests, A/B runs). */
-  s->throughput = s->n_problems > s->n_cu;
+  s->throughput = n_run > s->n_cu;
   s->packed = false;
   s->widened = 0;
   bool forced = false;
@@ -1438,13 +1548,13 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
       double a = 0.0, b = 0.0;
       if (sscanf(e, "%lf,%lf", &a, &b) == 2 && a > 0.0 && b > 0.0) lat_rate = a, thr_rate = b;
     }
-    std::vector<double> len((size_t)s->n_problems);
+    std::vector<double> len((size_t)n_run);
     double rest = 0.0;
-    for (int k = 0; k < s->n_problems; k++) {
-      len[(size_t)k] = (double)s->contig_n[(size_t)s->prob_contig[(size_t)s->order[(size_t)k]]];
+    for (int k = 0; k < n_run; k++) {
+      len[(size_t)k] = (double)s->contig_n[(size_t)s->prob_contig[(size_t)run_order[(size_t)k]]];
       rest += len[(size_t)k];
     }
-    const int l_max = std::max(0, s->n_cu - 16 < s->n_problems ? s->n_cu - 16 : s->n_problems - 1);
+    const int l_max = std::max(0, s->n_cu - 16 < n_run ? s->n_cu - 16 : n_run - 1);
     /* the predicted end of the set with problems [0, l) on the latency build and [l, n) packed
      * per_cu to a CU at `rate` each, minimised over l */
     auto plan = [&](double per_cu, double rate, int &best_l) -> double {
@@ -1478,7 +1588,7 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
       for (int k = 0; k < L; k++) on_lat += len[(size_t)k];
       fprintf(stderr, "peakseg_hip timing: plan: %d problems, %d on the latency build (predicted end "
                       "%.2f s), the rest %s (work %.2f s, longest %.2f s); rates %.0f / %.0f per s; "
-                      "all on thr %.2f s, all on pk %.2f s\n", s->n_problems, L,
+                      "all on thr %.2f s, all on pk %.2f s\n", n_run, L,
               L > 0 ? len[0] / lat_rate : 0.0, s->packed ? "pk" : "thr",
               (rest - on_lat) / ((double)(s->n_cu - L) * per_cu * rate), len[(size_t)L] / rate,
               lat_rate, thr_rate, t_thr, t_pk);
@@ -1489,7 +1599,7 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
    * and launches THOSE problems again: a problem that ran out of arena was parked by the kernel
    * and goes on at the data point it had reached (the arena grows by a segment, its records
    * stay in place); the others start over.  Finished problems are never computed twice. */
-  std::vector<int> todo(s->order); /* launch order: longest contig first */
+  std::vector<int> todo(run_order); /* launch order: longest contig first */
   std::fill(s->resume_t.begin(), s->resume_t.end(), 0);
   if (s->can_park) HIP_TRY(hipMemsetAsync(s->d_resume, 0, sizeof(int) * (size_t)s->n_problems, s->stream));
   HIP_TRY(hipMemsetAsync(s->d.ar_next_chunk, 0, sizeof(unsigned long long), s->stream));
@@ -1498,12 +1608,13 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
   s->steps_run = 0;
   s->live_blocks_added = 0;
   s->pack_total = -1;
+  s->segs_total = -1;
   s->parks = 0;
   s->park_pool_pieces = 0;
   float total_ms = 0.f;
   hipEvent_t ev_packed_end = nullptr; /* (diagnostic, PEAKSEG_HIP_TIMING) */
   int arena_rounds = 0;               /* launches of this solve that ran out of arena */
-  for (int attempt = 0;; attempt++) {
+  for (int attempt = 0; n_run > 0; attempt++) {
     if (s->ckpt_interval > 0) {
       const unsigned long long B = 1ull << s->d.ar_block_log2;
       const unsigned long long per_block = s->d.ckpt_region ? B / s->d.ckpt_region : 0ull;
@@ -1522,6 +1633,8 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
     s->d.ar_live = live ? s->h_live : nullptr;
     s->d.ar_used = s->h_used;
     psd::DeviceArgs d_run = s->d;
+    d_run.prob_order = d_order_first;
+    d_run.n_problems = n_todo;
     if (relaunch) {
       /* only the unfinished problems, in their original order */
       HIP_TRY(hipMemcpyAsync(s->d_order_sub, todo.data(), sizeof(int) * (size_t)n_todo,
@@ -1557,8 +1670,9 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
       const int L = s->n_lat_mixed;
       psd::DeviceArgs d_lat = s->d, d_thr = s->d;
       d_lat.n_problems = L;
-      d_thr.n_problems = s->n_problems - L;
-      d_thr.prob_order = s->d.prob_order + L;
+      d_lat.prob_order = d_order_first;
+      d_thr.n_problems = n_run - L;
+      d_thr.prob_order = d_order_first + L;
       HIP_TRY(hipStreamWaitEvent(s->stream2, s->ev[0], 0));
       /* A latency-build workgroup needs every register of a CU: once the packed part has put
        * a workgroup on each CU it would find none free before the packed part has drained,
@@ -1816,10 +1930,15 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
     }
     todo.swap(again);
   }
+  if (n_run == 0) { /* nothing but closed forms: no launch */
+    if (forward_ms) *forward_ms = 0.f;
+    if (backtrack_ms) *backtrack_ms = 0.f;
+  }
   if (s->packed && !forced && (long long)s->widened * 20 > (long long)s->n_problems)
     g_pk_handed_over_many.store(1);
 #ifndef PSD_EMU /* (the emulator's timings say nothing about the hardware) */
-  if (s->launches == 1 && s->n_lat_mixed == 0 && s->ckpt_interval == 0 && total_ms > 500.f) {
+  if (s->launches == 1 && s->n_lat_mixed == 0 && s->ckpt_interval == 0 && total_ms > 500.f &&
+      n_run == s->n_problems) {
     /* a clean single launch: the longest problem's data points / kernel time is the rate of
      * that build (the throughput build only while every workgroup was resident at once) */
     int longest = 0;
@@ -2144,6 +2263,452 @@ extern "C" int peakseg_hip_problem_set_max_spin(psd_problem_set *s, int p) {
   return s->results[(size_t)p].max_spin;
 }
 
+
+/* ---- dense coverage: run-length encoding on the device (dense_encode.h) -------------------- */
+
+namespace {
+
+struct DenseEncoded {
+  int *count = nullptr, *weight = nullptr, *run_end = nullptr; /* device, total_runs entries */
+  long long total_runs = 0;
+  std::vector<psd::dense::ContigStats> stats;
+  std::vector<long long> run_off;
+  float ms[3] = {0.f, 0.f, 0.f}; /* count, scan, scatter */
+  double upload_s = 0.0;
+};
+
+struct DenseScratch { /* device memory of one encoding, freed when it ends */
+  std::vector<void *> mem;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~DenseScratch() {
+    for (void *q : mem) (void)hipFree(q);
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  template <class T>
+  int get(T **p, size_t n) {
+    void *q = nullptr;
+    const size_t bytes = (n ? n : 1) * sizeof(T);
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) {
+      set_error("dense counts: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+      return ERROR_DEVICE_MEMORY;
+    }
+    mem.push_back(q);
+    *p = (T *)q;
+    return 0;
+  }
+};
+
+/* what the host can see of a dense call (after the penalties, before the device) */
+int dense_check_lengths(int n_contigs, const long long *n_bases) {
+  if (n_contigs <= 0 || !n_bases) {
+    set_error("dense counts: no contig");
+    return ERROR_NO_DATA;
+  }
+  for (int c = 0; c < n_contigs; c++)
+    if (n_bases[c] <= 0) {
+      set_error("dense counts: contig %d has no data", c);
+      return ERROR_NO_DATA;
+    }
+  for (int c = 0; c < n_contigs; c++)
+    if (n_bases[c] >= (1ll << 31)) {
+      set_error("dense counts: contig %d has %lld bases, 2^31 or more", c, n_bases[c]);
+      return ERROR_DENSE_ARGUMENTS;
+    }
+  return 0;
+}
+
+/* Stage 1 alone.  The device is set.  On success the three output arrays belong to the caller. */
+int dense_encode(int n_contigs, const long long *n_bases, const int *const *counts,
+                 int counts_on_device, DenseEncoded &enc) {
+  namespace dn = psd::dense;
+  DenseScratch scratch;
+  const auto t_upload = std::chrono::steady_clock::now();
+  std::vector<dn::Contig> contigs((size_t)n_contigs);
+  long long n_tiles = 0;
+  if (counts_on_device) {
+    for (int c = 0; c < n_contigs; c++) {
+      const unsigned long long addr = (unsigned long long)counts[c];
+      if (!counts[c] || (addr & 3ull)) {
+        set_error("dense counts: contig %d: the device address is %s", c,
+                  counts[c] ? "not a multiple of 4" : "NULL");
+        return ERROR_DENSE_ARGUMENTS;
+      }
+      contigs[(size_t)c].lead = (int)((addr >> 2) & 3ull);
+      contigs[(size_t)c].base = counts[c] - contigs[(size_t)c].lead;
+    }
+  } else {
+    /* the library's own copy: the contigs one after the other, each at a multiple of 16 bytes */
+    long long total = 0;
+    for (int c = 0; c < n_contigs; c++) total += (n_bases[c] + 3) & ~3ll;
+    int *d_in = nullptr;
+    int st = scratch.get(&d_in, (size_t)total);
+    if (st) return st;
+    long long off = 0;
+    for (int c = 0; c < n_contigs; c++) {
+      if (!counts || !counts[c]) {
+        set_error("dense counts: contig %d: NULL", c);
+        return ERROR_DENSE_ARGUMENTS;
+      }
+      HIP_TRY(hipMemcpy(d_in + off, counts[c], sizeof(int) * (size_t)n_bases[c], hipMemcpyHostToDevice));
+      contigs[(size_t)c].lead = 0;
+      contigs[(size_t)c].base = d_in + off;
+      off += (n_bases[c] + 3) & ~3ll;
+    }
+  }
+  for (int c = 0; c < n_contigs; c++) {
+    dn::Contig &k = contigs[(size_t)c];
+    k.n = n_bases[c];
+    k.tile_first = n_tiles;
+    k.run_off = 0;
+    k.pad = 0;
+    n_tiles += (k.lead + k.n + dn::TILE - 1) / dn::TILE;
+  }
+  /* (a grid dimension times the workgroup size stays below 2^32) */
+  if (n_tiles >= (1ll << 24)) {
+    set_error("dense counts: %lld tiles of %d bases in one call, 2^24 or more", n_tiles, dn::TILE);
+    return ERROR_DENSE_ARGUMENTS;
+  }
+  std::vector<int> tile_contig((size_t)n_tiles);
+  for (int c = 0; c < n_contigs; c++) {
+    const long long end = c + 1 < n_contigs ? contigs[(size_t)c + 1].tile_first : n_tiles;
+    std::fill(tile_contig.begin() + contigs[(size_t)c].tile_first, tile_contig.begin() + end, c);
+  }
+  dn::Contig *d_contigs = nullptr;
+  int *d_tile_contig = nullptr;
+  dn::TileInfo *d_tiles = nullptr;
+  dn::TileScan *d_scan = nullptr;
+  dn::ContigStats *d_stats = nullptr;
+  int st = 0;
+  if ((st = scratch.get(&d_contigs, (size_t)n_contigs)) ||
+      (st = scratch.get(&d_tile_contig, (size_t)n_tiles)) ||
+      (st = scratch.get(&d_tiles, (size_t)n_tiles)) || (st = scratch.get(&d_scan, (size_t)n_tiles)) ||
+      (st = scratch.get(&d_stats, (size_t)n_contigs)))
+    return st;
+  HIP_TRY(hipMemcpy(d_contigs, contigs.data(), sizeof(dn::Contig) * (size_t)n_contigs, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_tile_contig, tile_contig.data(), sizeof(int) * (size_t)n_tiles, hipMemcpyHostToDevice));
+  for (auto &e : scratch.ev) HIP_TRY(hipEventCreate(&e));
+  hipStream_t stream = (hipStream_t) nullptr;
+  enc.upload_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_upload).count();
+  HIP_TRY(hipEventRecord(scratch.ev[0], stream));
+  hipLaunchKernelGGL(dn::count_kernel, dim3((unsigned)n_tiles), dim3(dn::THREADS), 0, stream,
+                     (const dn::Contig *)d_contigs, (const int *)d_tile_contig, d_tiles);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(scratch.ev[1], stream));
+  hipLaunchKernelGGL(dn::scan_kernel, dim3((unsigned)n_contigs), dim3(dn::THREADS), 0, stream,
+                     (const dn::Contig *)d_contigs, (const dn::TileInfo *)d_tiles, d_scan, d_stats);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(scratch.ev[2], stream));
+  enc.stats.resize((size_t)n_contigs);
+  HIP_TRY(hipMemcpy(enc.stats.data(), d_stats, sizeof(dn::ContigStats) * (size_t)n_contigs,
+                    hipMemcpyDeviceToHost));
+  enc.run_off.assign((size_t)n_contigs, 0);
+  long long total_runs = 0;
+  for (int c = 0; c < n_contigs; c++) {
+    const dn::ContigStats &cs = enc.stats[(size_t)c];
+    if (cs.mn < 0) {
+      set_error("dense counts: contig %d holds a negative count (minimum %d)", c, cs.mn);
+      return ERROR_DENSE_ARGUMENTS;
+    }
+    if (cs.sum >= (1ll << 53)) {
+      set_error("dense counts: contig %d: the counts sum to %lld, 2^53 or more", c, cs.sum);
+      return ERROR_DENSE_ARGUMENTS;
+    }
+    if (cs.runs >= (1ll << 30)) {
+      set_error("dense counts: contig %d has %lld runs, 2^30 or more", c, cs.runs);
+      return ERROR_DENSE_ARGUMENTS;
+    }
+    enc.run_off[(size_t)c] = total_runs;
+    contigs[(size_t)c].run_off = total_runs;
+    total_runs += cs.runs;
+  }
+  enc.total_runs = total_runs;
+  HIP_TRY(hipMemcpy(d_contigs, contigs.data(), sizeof(dn::Contig) * (size_t)n_contigs, hipMemcpyHostToDevice));
+  int *out[3] = {nullptr, nullptr, nullptr};
+  for (auto &q : out) {
+    const hipError_t e = hipMalloc(&q, sizeof(int) * (size_t)total_runs);
+    if (e != hipSuccess) {
+      set_error("dense counts: hipMalloc(%lld runs) failed: %s", total_runs, hipGetErrorString(e));
+      for (auto &f : out)
+        if (f) (void)hipFree(f);
+      return ERROR_DEVICE_MEMORY;
+    }
+  }
+  hipError_t e = hipEventRecord(scratch.ev[3], stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(dn::scatter_kernel, dim3((unsigned)n_tiles), dim3(dn::THREADS), 0, stream,
+                       (const dn::Contig *)d_contigs, (const int *)d_tile_contig,
+                       (const dn::TileScan *)d_scan, out[0], out[1], out[2]);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(scratch.ev[4], stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&enc.ms[0], scratch.ev[0], scratch.ev[1]);
+  if (e == hipSuccess) e = hipEventElapsedTime(&enc.ms[1], scratch.ev[1], scratch.ev[2]);
+  if (e == hipSuccess) e = hipEventElapsedTime(&enc.ms[2], scratch.ev[3], scratch.ev[4]);
+  if (e != hipSuccess) {
+    set_error("dense counts: the encoder failed: %s", hipGetErrorString(e));
+    for (auto &f : out) (void)hipFree(f);
+    return ERROR_DEVICE_SOLVER;
+  }
+  enc.count = out[0];
+  enc.weight = out[1];
+  enc.run_end = out[2];
+  return 0;
+}
+
+thread_local float g_dense_ms[3] = {0.f, 0.f, 0.f};
+
+}  // namespace
+
+extern "C" int peakseg_hip_dense_tile_bases(void) { return psd::dense::TILE; }
+
+extern "C" int peakseg_hip_dense_last_encode_ms(float *count_ms, float *scan_ms, float *scatter_ms) {
+  if (count_ms) *count_ms = g_dense_ms[0];
+  if (scan_ms) *scan_ms = g_dense_ms[1];
+  if (scatter_ms) *scatter_ms = g_dense_ms[2];
+  return 0;
+}
+
+extern "C" int peakseg_hip_dense_encode_probe(int device, int n_contigs, const long long *n_bases,
+                                              const int *const *counts, int counts_on_device,
+                                              long long *runs_out, int *count_out, int *weight_out,
+                                              int *run_end_out, int *min_out, int *max_out,
+                                              long long *sum_out) {
+  int st = dense_check_lengths(n_contigs, n_bases);
+  if (st) return st;
+  if (peakseg_hip_device_count() <= device || device < 0) {
+    set_error("no HIP device %d visible (this library has no CPU fallback)", device);
+    return ERROR_NO_HIP_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(device));
+  DenseEncoded enc;
+  st = dense_encode(n_contigs, n_bases, counts, counts_on_device, enc);
+  if (st) return st;
+  for (int k = 0; k < 3; k++) g_dense_ms[k] = enc.ms[k];
+  for (int c = 0; c < n_contigs; c++) {
+    if (runs_out) runs_out[c] = enc.stats[(size_t)c].runs;
+    if (min_out) min_out[c] = enc.stats[(size_t)c].mn;
+    if (max_out) max_out[c] = enc.stats[(size_t)c].mx;
+    if (sum_out) sum_out[c] = enc.stats[(size_t)c].sum;
+  }
+  const size_t bytes = sizeof(int) * (size_t)enc.total_runs;
+  hipError_t e = hipSuccess;
+  if (count_out) e = hipMemcpy(count_out, enc.count, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && weight_out) e = hipMemcpy(weight_out, enc.weight, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && run_end_out) e = hipMemcpy(run_end_out, enc.run_end, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(enc.count);
+  (void)hipFree(enc.weight);
+  (void)hipFree(enc.run_end);
+  if (e != hipSuccess) {
+    set_error("dense counts: download failed: %s", hipGetErrorString(e));
+    return ERROR_DEVICE_SOLVER;
+  }
+  return 0;
+}
+
+extern "C" int peakseg_hip_problem_set_create_dense(int device, int n_contigs,
+                                                    const long long *contig_n_bases,
+                                                    const int *const *contig_counts,
+                                                    int counts_on_device, int n_problems,
+                                                    const int *problem_contig,
+                                                    const double *problem_penalty,
+                                                    unsigned long long arena_pieces,
+                                                    psd_problem_set **out) {
+  *out = nullptr;
+  /* penalties first: the reference validates them before it opens its input (drv:145-159) */
+  for (int p = 0; p < n_problems; p++) {
+    const double pen = problem_penalty[p];
+    if (pen == INFINITY) continue;
+    if (!std::isfinite(pen)) {
+      set_error("problem %d: penalty is not finite", p);
+      return ERROR_PENALTY_NOT_FINITE;
+    }
+    if (pen < 0) {
+      set_error("problem %d: penalty is negative", p);
+      return ERROR_PENALTY_NEGATIVE;
+    }
+  }
+  int st = dense_check_lengths(n_contigs, contig_n_bases);
+  if (st) return st;
+  if (peakseg_hip_device_count() <= device || device < 0) {
+    set_error("no HIP device %d visible (this library has no CPU fallback)", device);
+    return ERROR_NO_HIP_DEVICE;
+  }
+  if (n_problems <= 0) {
+    set_error("empty problem set");
+    return ERROR_DEVICE_SOLVER;
+  }
+  for (int p = 0; p < n_problems; p++)
+    if (problem_contig[p] < 0 || problem_contig[p] >= n_contigs) {
+      set_error("problem %d names contig %d", p, problem_contig[p]);
+      return ERROR_DEVICE_SOLVER;
+    }
+  HIP_TRY(hipSetDevice(device));
+  CreateLaps lap;
+  DenseEncoded enc;
+  st = dense_encode(n_contigs, contig_n_bases, contig_counts, counts_on_device, enc);
+  if (st) return st;
+  for (int k = 0; k < 3; k++) g_dense_ms[k] = enc.ms[k];
+  if (lap.on) {
+    fprintf(stderr, "peakseg_hip timing: create: %-26s %8.3f s\n",
+            counts_on_device ? "dense: tables" : "dense: upload, tables", enc.upload_s);
+    fprintf(stderr, "peakseg_hip timing: create: %-26s %8.3f s\n", "dense: count kernel", enc.ms[0] / 1e3);
+    fprintf(stderr, "peakseg_hip timing: create: %-26s %8.3f s\n", "dense: scan kernel", enc.ms[1] / 1e3);
+    fprintf(stderr, "peakseg_hip timing: create: %-26s %8.3f s\n", "dense: scatter kernel", enc.ms[2] / 1e3);
+  }
+  lap("dense: encoder in all");
+  psd_problem_set *s = new psd_problem_set();
+  s->device = device;
+  s->n_contigs = n_contigs;
+  s->n_problems = n_problems;
+  s->dense = true;
+  for (int *q : {enc.count, enc.weight, enc.run_end}) s->allocs.push_back(q);
+  s->bytes += 12ull * (unsigned long long)enc.total_runs;
+  s->d.count = enc.count;
+  s->d.weight = enc.weight;
+  s->d_run_end = enc.run_end;
+  std::vector<double> min_lm((size_t)n_contigs), max_lm((size_t)n_contigs);
+  for (int c = 0; c < n_contigs; c++) {
+    const psd::dense::ContigStats &cs = enc.stats[(size_t)c];
+    s->contig_n.push_back((int)cs.runs);
+    s->contig_off.push_back(enc.run_off[(size_t)c]);
+    s->contig_bases.push_back(contig_n_bases[c]);
+    s->contig_sum.push_back(cs.sum);
+    s->contig_constant.push_back(cs.mn == cs.mx);
+    /* psd_log is strictly increasing on the integers: the logs of the integer extremes are the
+     * extremes of the logs (drv:198-204) */
+    min_lm[(size_t)c] = psd_log((double)cs.mn);
+    max_lm[(size_t)c] = psd_log((double)cs.mx);
+  }
+  s->total_bins = enc.total_runs;
+  if ((st = dev_alloc(s, &s->d_order_run, (size_t)n_problems))) {
+    peakseg_hip_problem_set_destroy(s);
+    return st;
+  }
+  return create_common(s, lap, min_lm, max_lm, nullptr, nullptr, problem_contig, problem_penalty,
+                       arena_pieces, out);
+}
+
+extern "C" long long peakseg_hip_problem_set_pack_segments(psd_problem_set *s,
+                                                           const int *first_chromStart,
+                                                           long long *rows_out,
+                                                           const int **chromStart_dev,
+                                                           const int **chromEnd_dev,
+                                                           const double **mean_dev) {
+  if (!s || !s->solved) return -1;
+  if (!s->dense) {
+    set_error("pack_segments: the set was not made from dense counts and has no run_end[]");
+    return -1;
+  }
+  if (hipSetDevice(s->device) != hipSuccess) return -1;
+  std::vector<long long> rows((size_t)6 * (size_t)s->n_problems);
+  long long *lay = rows.data() + (size_t)3 * (size_t)s->n_problems;
+  long long total = 0;
+  for (int p = 0; p < s->n_problems; p++) {
+    const psd::ProbResult &r = s->results[(size_t)p];
+    const long long n = r.status == 0 ? r.n_segments : 0;
+    const int c = s->prob_contig[(size_t)p];
+    const long long first = first_chromStart ? first_chromStart[c] : 0;
+    if (first < 0 || first + s->contig_bases[(size_t)c] > 2147483647ll) {
+      set_error("pack_segments: contig %d: chromStart %lld + %lld bases is no 32-bit coordinate", c,
+                first, s->contig_bases[(size_t)c]);
+      return -1;
+    }
+    rows[(size_t)3 * p] = total;
+    rows[(size_t)3 * p + 1] = n;
+    rows[(size_t)3 * p + 2] = s->prob_seg_off[(size_t)p];
+    lay[(size_t)3 * p] = s->contig_off[(size_t)c];
+    lay[(size_t)3 * p + 1] = first;
+    lay[(size_t)3 * p + 2] = s->contig_bases[(size_t)c];
+    if (rows_out) rows_out[p] = n;
+    total += n;
+  }
+  if (total > s->segs_capacity || !s->d_segs_rows) {
+    for (void *q : {(void *)s->d_segs_start, (void *)s->d_segs_end, (void *)s->d_segs_mean}) {
+      if (!q) continue;
+      forget_alloc(s, q);
+      (void)hipFree(q);
+    }
+    s->bytes -= (unsigned long long)s->segs_capacity * 16ull;
+    s->d_segs_start = s->d_segs_end = nullptr;
+    s->d_segs_mean = nullptr;
+    s->segs_capacity = 0;
+    if (dev_alloc(s, &s->d_segs_start, (size_t)total) || dev_alloc(s, &s->d_segs_end, (size_t)total) ||
+        dev_alloc(s, &s->d_segs_mean, (size_t)total))
+      return -1;
+    s->segs_capacity = total > 0 ? total : 1;
+    if (!s->d_segs_rows && dev_alloc(s, &s->d_segs_rows, rows.size())) return -1;
+  }
+  if (hipMemcpy(s->d_segs_rows, rows.data(), rows.size() * sizeof(long long),
+                hipMemcpyHostToDevice) != hipSuccess)
+    return -1;
+  hipLaunchKernelGGL(psd::dense::pack_segments_kernel, dim3((unsigned)s->n_problems), dim3(256), 0,
+                     s->stream, (const int *)s->d.seg_start, (const double *)s->d.seg_mean,
+                     (const long long *)s->d_segs_rows,
+                     (const long long *)(s->d_segs_rows + (size_t)3 * (size_t)s->n_problems),
+                     (const int *)s->d_run_end, s->d_segs_start, s->d_segs_end, s->d_segs_mean);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) {
+    set_error("packing the segments failed");
+    return -1;
+  }
+  s->segs_total = total;
+  if (chromStart_dev) *chromStart_dev = s->d_segs_start;
+  if (chromEnd_dev) *chromEnd_dev = s->d_segs_end;
+  if (mean_dev) *mean_dev = s->d_segs_mean;
+  return total;
+}
+
+extern "C" int peakseg_hip_problem_set_packed_segments_download(psd_problem_set *s,
+                                                                int *chromStart_out,
+                                                                int *chromEnd_out,
+                                                                double *mean_out) {
+  if (!s || s->segs_total < 0) return -1;
+  const size_t n = (size_t)s->segs_total;
+  if (n == 0) return 0;
+  if (hipMemcpy(chromStart_out, s->d_segs_start, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(chromEnd_out, s->d_segs_end, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(mean_out, s->d_segs_mean, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("download of the packed segments failed");
+    return -1;
+  }
+  return 0;
+}
+
+/* the reference's loss row: write_dp_outputs and write_trivial in peakseg_files.h */
+extern "C" int peakseg_hip_problem_set_loss(psd_problem_set *s, int p, double *out) {
+  if (!s || !s->solved || !out || p < 0 || p >= s->n_problems) return -1;
+  const psd::ProbResult &r = s->results[(size_t)p];
+  if (r.status != 0) return -1;
+  const int c = s->prob_contig[(size_t)p];
+  const double cum_weight = (double)s->contig_bases[(size_t)c];
+  const int n = s->contig_n[(size_t)c];
+  const double penalty = s->prob_penalty[(size_t)p];
+  out[0] = penalty;
+  out[3] = (double)(int)cum_weight;
+  out[4] = (double)n;
+  if (trivial_model(s, p)) {
+    const double best_cost = trivial_best_cost(s, c);
+    out[1] = 1;
+    out[2] = 0;
+    out[5] = best_cost / cum_weight;
+    out[6] = best_cost;
+    out[7] = out[8] = out[9] = 0;
+    return 0;
+  }
+  const int n_peaks = (r.n_segments - 1) / 2;
+  const double total_intervals = (double)r.total_intervals;
+  out[1] = (double)r.n_segments;
+  out[2] = (double)n_peaks;
+  out[5] = r.best_cost;
+  out[6] = r.best_cost * cum_weight - penalty * n_peaks;
+  out[7] = (double)r.n_equality;
+  out[8] = total_intervals / (n * 2);
+  out[9] = (double)r.max_intervals;
+  return 0;
+}
+
 /* ---- file-level solver (the reference's boundary), directory-level batch with the cache
  *      protocol, resident penalty search ----------------------------------------------------- */
 #include "peakseg_files.h"
@@ -2196,6 +2761,12 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
     case ERROR_NO_HIP_DEVICE:
       snprintf(buf, buf_len,
                "error code %d: no HIP device (MI355X) is visible and this solver has no CPU path",
+               status);
+      break;
+    case ERROR_DENSE_ARGUMENTS:
+      snprintf(buf, buf_len,
+               "error code %d: dense counts that cannot be solved (2^31 or more bases, a negative "
+               "count, counts that sum to 2^53 or more, or 2^30 or more runs in a contig)",
                status);
       break;
     default:

@@ -8,12 +8,41 @@ import numpy as np
 from . import _native
 
 
+def _dense_pointer(k, v, device):
+    """(address, length, "host" | "device", the object that keeps the memory alive) of contig k
+    of ProblemSet.from_dense; ValueError for what cannot be passed as it is."""
+    if isinstance(v, np.ndarray):
+        if v.dtype != np.int32:
+            raise ValueError("from_dense: contig %d has dtype %s, not int32" % (k, v.dtype))
+        if v.ndim != 1 or not v.flags["C_CONTIGUOUS"]:
+            raise ValueError("from_dense: contig %d is not a contiguous 1-d array" % k)
+        return v.ctypes.data, v.shape[0], "host", v
+    if type(v).__module__.split(".")[0] == "torch" and hasattr(v, "data_ptr"):
+        import torch
+        if v.dtype != torch.int32:
+            raise ValueError("from_dense: contig %d has dtype %s, not int32" % (k, v.dtype))
+        if v.dim() != 1 or not v.is_contiguous():
+            raise ValueError("from_dense: contig %d is not a contiguous 1-d tensor" % k)
+        if v.device.type == "cuda":
+            index = v.device.index if v.device.index is not None else torch.cuda.current_device()
+            if index != device:
+                raise ValueError("from_dense: contig %d is on cuda:%d, the set on device %d"
+                                 % (k, index, device))
+            return v.data_ptr(), v.shape[0], "device", v
+        if v.device.type != "cpu":
+            raise ValueError("from_dense: contig %d is on device %s" % (k, v.device))
+        return v.data_ptr(), v.shape[0], "host", v
+    raise ValueError("from_dense: contig %d is a %s, not an int32 numpy array or torch tensor"
+                     % (k, type(v).__name__))
+
+
 class ProblemSet:
     """contigs: list of (count, weight) int32 arrays; problems: list of (contig_index, penalty)."""
 
     def __init__(self, contigs, problems, device=0, arena_pieces=0, lib=None):
         self._lib = lib or _native.lib
         self._h = ctypes.c_void_p()
+        self.dense = False
         self.contigs = [(np.ascontiguousarray(c, dtype=np.int32),
                          np.ascontiguousarray(w, dtype=np.int32)) for c, w in contigs]
         self.problems = [(int(c), float(p)) for c, p in problems]
@@ -31,6 +60,103 @@ class ProblemSet:
             raise RuntimeError("peakseg_hip_problem_set_create: status %d: %s" % (
                 st, self._lib.peakseg_hip_last_error().decode()))
         self.bins_per_solve = sum(len(self.contigs[c][0]) for c, _ in self.problems)
+
+    @classmethod
+    def from_dense(cls, contigs, problems, device=0, arena_pieces=0, lib=None):
+        """The set of DENSE coverage: a contig is a 1-d contiguous int32 numpy array or torch
+        tensor with one count per base, and the run-length encoding happens on the device
+        (peakseg_hip_problem_set_create_dense).  A tensor on cuda:`device` is read in place
+        through its data_ptr(), without a copy; numpy arrays and CPU tensors are uploaded by the
+        library.  All contigs of one call live on the same side.  The set's contigs are the runs:
+        problem p's segment table indexes them, segment_columns() gives base coordinates."""
+        self = cls.__new__(cls)
+        self._lib = lib or _native.lib
+        self._h = ctypes.c_void_p()
+        self.dense = True
+        self.problems = [(int(c), float(p)) for c, p in problems]
+        if len(contigs) == 0:
+            raise ValueError("from_dense: no contig")
+        keep, ptrs, sides = [], [], []
+        for k, v in enumerate(contigs):
+            ptr, n, side, ref = _dense_pointer(k, v, device)
+            keep.append(ref)
+            ptrs.append(ptr)
+            sides.append(side)
+            if n == 0:
+                ptrs[-1] = 0
+        if len(set(sides)) != 1:
+            k = next(i for i, sd in enumerate(sides) if sd != sides[0])
+            raise ValueError("from_dense: contig %d is in %s memory but contig 0 is in %s memory; "
+                             "one call takes one kind" % (k, sides[k], sides[0]))
+        self.contig_bases = [int(r.shape[0]) for r in keep]
+        nc = len(keep)
+        n_bases = (ctypes.c_longlong * nc)(*self.contig_bases)
+        cptr = (ctypes.c_void_p * nc)(*ptrs)
+        npb = len(self.problems)
+        pc = (ctypes.c_int * max(npb, 1))(*[c for c, _ in self.problems])
+        pp = (ctypes.c_double * max(npb, 1))(*[p for _, p in self.problems])
+        st = self._lib.peakseg_hip_problem_set_create_dense(
+            device, nc, n_bases, cptr, 1 if sides[0] == "device" else 0, npb, pc, pp,
+            ctypes.c_ulonglong(arena_pieces), ctypes.byref(self._h))
+        del keep  # (the library holds no reference to the caller's buffers after the call)
+        if st != 0:
+            err = RuntimeError("peakseg_hip_problem_set_create_dense: status %d: %s" % (
+                st, self._lib.peakseg_hip_last_error().decode()))
+            err.status = st
+            raise err
+        self.contigs = None
+        self.bins_per_solve = None
+        return self
+
+    def segment_columns(self, first_chromStart=None, torch_device=None):
+        """The reference's segments table of every problem of a solved set made by from_dense
+        (peakseg_hip_problem_set_pack_segments): chromStart, chromEnd and mean in the
+        reference's row order (last segment first); a row's status is its parity (even:
+        background, odd: peak).  first_chromStart: the coordinate of each CONTIG's first base
+        (default 0).  Without torch_device: a list over problems of (chromStart int32[],
+        chromEnd int32[], mean float64[]) numpy arrays.  With torch_device:
+        (rows int64 numpy[k + 1] -- problem p's rows are rows[p]:rows[p + 1] --, chromStart,
+        chromEnd, mean) where the three are tensors that alias the library's packed buffers:
+        nothing is downloaded, and they are valid until the next solve() / close()."""
+        k = len(self.problems)
+        rows = np.zeros(k, dtype=np.int64)
+        first = None
+        if first_chromStart is not None:
+            first = np.ascontiguousarray(first_chromStart, dtype=np.int32)
+            if first.shape != (len(self.contig_bases),):
+                raise ValueError("first_chromStart: one value per contig")
+        p1, p2, p3 = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        total = self._lib.peakseg_hip_problem_set_pack_segments(
+            self._h, first.ctypes.data if first is not None else None, rows.ctypes.data,
+            ctypes.byref(p1), ctypes.byref(p2), ctypes.byref(p3))
+        if total < 0:
+            raise RuntimeError("pack_segments: %s" % self._lib.peakseg_hip_last_error().decode())
+        total = int(total)
+        offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            return (offs, device_array(p1.value or 0, total, np.int32, dev),
+                    device_array(p2.value or 0, total, np.int32, dev),
+                    device_array(p3.value or 0, total, np.float64, dev))
+        start = np.empty(total, dtype=np.int32)
+        end = np.empty(total, dtype=np.int32)
+        mean = np.empty(total, dtype=np.float64)
+        if self._lib.peakseg_hip_problem_set_packed_segments_download(
+                self._h, start.ctypes.data, end.ctypes.data, mean.ctypes.data) != 0:
+            raise RuntimeError("packed_segments_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        return [(start[offs[p]:offs[p + 1]], end[offs[p]:offs[p + 1]], mean[offs[p]:offs[p + 1]])
+                for p in range(k)]
+
+    def loss(self, p):
+        """The ten fields of the reference's loss.tsv row of problem p (api.col_name_list["loss"]),
+        as float64."""
+        out = (ctypes.c_double * 10)()
+        if self._lib.peakseg_hip_problem_set_loss(self._h, p, out) != 0:
+            raise RuntimeError("no loss row for problem %d" % p)
+        return np.array(out[:], dtype=np.float64)
 
     def solve(self):
         """Forward DP + backtrack for every problem; returns (forward_ms, backtrack_ms)."""

@@ -1,0 +1,227 @@
+#!/usr/bin/env python3
+"""Timing of the dense in-memory path on the MI355X.
+
+(a) the encoder alone on one contig of 2.5e8 bases (synthetic.poisson_coverage(10**7) expanded on
+    the device), (b) the same on many contigs of 10 k bins (about 2.5e5 bases each): HIP events of
+    the three launches, warmed, --reps repetitions, minimum / median / maximum, achieved bytes/s by
+    the encoder's algorithmic traffic 8 B + 12 R (B bases read twice, R runs x three int32 written)
+    and its share of the 6.29 TB/s a plain copy reaches on this chip.
+(c) end to end for set (b) with one penalty per contig, alternating in one process:
+      dense_api      PeakSegFPOP_dense on device tensors (data frames out)
+      dense_arrays   ProblemSet.from_dense + solve + segment_columns + loss on device tensors
+      dense_host     the same from host numpy arrays (upload included)
+      files          PeakSegFPOP_disk_batch on bedGraph files written beforehand (file to file)
+      host_encoded   numpy run-length encoding of the host vectors + ProblemSet + solve + a
+                     segments call per problem
+    The legs' results are compared for equality before any time is printed.
+
+usage: python tools/dense_timing.py [--contigs 6144] [--reps 20] [--e2e-reps 2] [--skip-long]
+One JSON line per part on stdout."""
+import argparse
+import ctypes
+import json
+import os
+import shutil
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import peaksegdisk_amd as psd  # noqa: E402
+from peaksegdisk_amd import ProblemSet, _native, synthetic  # noqa: E402
+
+COPY_BW = 6.29e12  # bytes/s of a plain copy on the MI355X (measured; the specification says 8e12)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--contigs", type=int, default=6144)
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--e2e-reps", type=int, default=2)
+ap.add_argument("--skip-long", action="store_true")
+ap.add_argument("--skip-e2e", action="store_true")
+args = ap.parse_args()
+lib = _native.lib
+
+
+def expand(cnt, width):
+    return torch.repeat_interleave(torch.from_numpy(cnt).to("cuda:0"),
+                                   torch.from_numpy(width).to("cuda:0"))
+
+
+def encoder_laps(tensors, reps):
+    nc = len(tensors)
+    nb = (ctypes.c_longlong * nc)(*[len(t) for t in tensors])
+    ptr = (ctypes.c_void_p * nc)(*[t.data_ptr() for t in tensors])
+    runs = np.zeros(nc, np.int64)
+    laps = []
+    torch.cuda.synchronize()
+    for k in range(reps + 3):
+        st = lib.peakseg_hip_dense_encode_probe(0, nc, nb, ptr, 1, runs.ctypes.data, None, None,
+                                                None, None, None, None)
+        assert st == 0, _native.last_error()
+        ms = [ctypes.c_float() for _ in range(3)]
+        lib.peakseg_hip_dense_last_encode_ms(*[ctypes.byref(m) for m in ms])
+        if k >= 3:  # warmed
+            laps.append([m.value for m in ms])
+    bases = sum(len(t) for t in tensors)
+    total = [sum(l) for l in laps]
+    traffic = 8.0 * bases + 12.0 * float(runs.sum())
+
+    def mmm(v):
+        return {"min": min(v), "median": statistics.median(v), "max": max(v)}
+    med = statistics.median(total)
+    return {"contigs": nc, "bases": bases, "runs": int(runs.sum()), "reps": reps,
+            "traffic_bytes": traffic,
+            "count_ms": mmm([l[0] for l in laps]), "scan_ms": mmm([l[1] for l in laps]),
+            "scatter_ms": mmm([l[2] for l in laps]), "total_ms": mmm(total),
+            "bytes_per_s_median": traffic / (med * 1e-3),
+            "share_of_copy_bandwidth": traffic / (med * 1e-3) / COPY_BW,
+            "bytes_per_s_best": traffic / (min(total) * 1e-3)}
+
+
+if not args.skip_long:
+    cs, ce, cnt = synthetic.poisson_coverage(10 ** 7, seed=1)
+    long_t = expand(cnt, (ce - cs).astype(np.int64))
+    print(json.dumps(dict(part="a_encoder_one_contig", **encoder_laps([long_t], args.reps))),
+          flush=True)
+    del long_t
+    torch.cuda.empty_cache()
+
+# set (b)
+grid = synthetic.penalty_grid()
+bins, tensors = [], []
+for k in range(args.contigs):
+    cs, ce, cnt = synthetic.poisson_coverage(10000, seed=k)
+    width = (ce - cs).astype(np.int64)
+    bins.append((cnt, width))
+    tensors.append(expand(cnt, width))
+print(json.dumps(dict(part="b_encoder_many_contigs", **encoder_laps(tensors, args.reps))),
+      flush=True)
+if args.skip_e2e:
+    sys.exit(0)
+
+pens = [grid[k % 64] for k in range(args.contigs)]
+problems = [(k, float(pens[k])) for k in range(args.contigs)]
+host_vectors = [np.repeat(c, w).astype(np.int32) for c, w in bins]
+
+
+def rle(x):
+    change = np.flatnonzero(np.diff(x) != 0)
+    ends = np.concatenate([change + 1, [len(x)]]).astype(np.int64)
+    starts = np.concatenate([[0], ends[:-1]]).astype(np.int64)
+    return x[starts], (ends - starts).astype(np.int32), ends.astype(np.int32)
+
+
+work = tempfile.mkdtemp(prefix="psd_dense_timing_")
+try:
+    files = []
+    t0 = time.time()
+    for k, v in enumerate(host_vectors):
+        count, weight, ends = rle(v)
+        d = os.path.join(work, "p%05d" % k)
+        os.mkdir(d)
+        files.append(os.path.join(d, "coverage.bedGraph"))
+        synthetic.write_bedgraph(files[-1], ends - weight, ends, count, chrom="chrT")
+    t_files = time.time() - t0
+    n = args.contigs
+    c_files = (ctypes.c_char_p * n)(*[os.fsencode(f) for f in files])
+    c_pens = (ctypes.c_char_p * n)(*[p.encode() for p in pens])
+    c_dbs = (ctypes.c_char_p * n)(*[os.fsencode(f + ".db") for f in files])
+    status = (ctypes.c_int * n)()
+
+    def leg_dense_api():
+        return psd.PeakSegFPOP_dense(tensors, [[float(p)] for p in pens], chrom="chrT")
+
+    def leg_dense_arrays(source=tensors):
+        s = ProblemSet.from_dense(source, problems)
+        try:
+            k_ms = s.solve()[0]
+            cols = s.segment_columns()
+            loss = [s.loss(p) for p in range(n)]
+            build = s.kernel_build
+        finally:
+            s.close()
+        return cols, loss, k_ms, build
+
+    def leg_dense_host():
+        return leg_dense_arrays(host_vectors)
+
+    def leg_files():
+        rc = lib.PeakSegFPOP_disk_batch(n, c_files, c_pens, c_dbs, status)
+        assert rc == 0, rc
+        return None
+
+    def leg_host_encoded():
+        enc = [rle(v) for v in host_vectors]
+        s = ProblemSet([(c, w) for c, w, _ in enc], problems)
+        try:
+            k_ms = s.solve()[0]
+            tables = [s.segments(p) for p in range(n)]
+        finally:
+            s.close()
+        return enc, tables, k_ms
+
+    legs = [("dense_api", leg_dense_api), ("dense_arrays", leg_dense_arrays),
+            ("dense_host", leg_dense_host), ("files", leg_files),
+            ("host_encoded", leg_host_encoded)]
+    times = {name: [] for name, _ in legs}
+    last = {}
+    for rep in range(args.e2e_reps + 1):  # (the first round warms every leg and is not counted)
+        for name, fn in legs:
+            t0 = time.time()
+            last[name] = fn()
+            if rep > 0:
+                times[name].append(time.time() - t0)
+    # equality of the legs' results, before any time is printed
+    cols, loss, k_ms_dense, build = last["dense_arrays"]
+    cols_h, loss_h, _, _ = last["dense_host"]
+    enc, tables, k_ms_host = last["host_encoded"]
+    api = last["dense_api"]
+    for p in range(n):
+        start, end, mean = cols[p]
+        assert all(np.array_equal(x, y) for x, y in zip(cols[p], cols_h[p])), p
+        assert np.array_equal(loss[p], loss_h[p]), p
+        idx, t_mean = tables[p]
+        ends = enc[p][2]
+        assert np.array_equal(np.where(idx < 0, 0, ends[np.maximum(idx, 0)]), start), p
+        assert np.array_equal(t_mean, mean), p
+        text = open("%s_penalty=%s_segments.bed" % (files[p], pens[p])).read()
+        want = "".join("chrT\t%d\t%d\t%s\t%g\n" % (a, b, "background" if r % 2 == 0 else "peak", m)
+                       for r, (a, b, m) in enumerate(zip(start.tolist(), end.tolist(),
+                                                         mean.tolist())))
+        assert text == want, p
+        row = open("%s_penalty=%s_loss.tsv" % (files[p], pens[p])).read().split("\t")
+        assert [float(x) for x in row] == loss[p].tolist(), p
+        seg = api[p][0].segments
+        assert seg["chromStart"].tolist() == start.tolist() and \
+            seg["mean"].tolist() == [float("%g" % m) for m in mean.tolist()], p
+    out = {"part": "c_end_to_end", "contigs": n, "data_points": int(sum(len(e[0]) for e in enc)),
+           "bases": int(sum(len(v) for v in host_vectors)), "kernel_build": build,
+           "solve_kernel_s_dense": k_ms_dense / 1e3, "solve_kernel_s_host_encoded": k_ms_host / 1e3,
+           "writing_the_bedGraph_files_s_not_in_any_leg": t_files,
+           "legs_equal": True, "reps": args.e2e_reps}
+    for name, _ in legs:
+        out[name + "_s"] = {"min": min(times[name]), "median": statistics.median(times[name]),
+                            "max": max(times[name])}
+    print(json.dumps(out), flush=True)
+    # where the dense path's time goes: the library's own laps, on stderr
+    os.environ["PEAKSEG_HIP_TIMING"] = "1"
+    t0 = time.time()
+    s = ProblemSet.from_dense(tensors, problems)
+    t1 = time.time()
+    s.solve()
+    t2 = time.time()
+    s.segment_columns()
+    t3 = time.time()
+    for p in range(n):
+        s.loss(p)
+    t4 = time.time()
+    s.close()
+    print(json.dumps({"part": "c_dense_arrays_phases", "from_dense_s": t1 - t0,
+                      "solve_s": t2 - t1, "segment_columns_s": t3 - t2, "loss_rows_s": t4 - t3}),
+          flush=True)
+finally:
+    shutil.rmtree(work, ignore_errors=True)
