@@ -351,6 +351,33 @@ long long peakseg_hip_problem_set_pack_segments(psd_problem_set *set, const int 
 int peakseg_hip_problem_set_packed_segments_download(psd_problem_set *set, int *chromStart_out,
                                                      int *chromEnd_out, double *mean_out);
 
+/* What every row of that segments table holds, from the runs resident in HBM: four more columns,
+ * packed in the same row order and at the same row offsets as pack_segments' three.  Row r of a
+ * problem covers the runs seg_start[r] + 1 ... seg_start[r - 1] of its contig (row 0: to the
+ * contig's last run; seg_start < 0: from run 0), and of those runs
+ *   sum          int64  the sum of count[i] * weight[i]: the reads under the segment
+ *   max          int32  the largest count[i]
+ *   summitStart  int32  first + run_end[i] - weight[i]   of the FIRST run in genomic order whose
+ *   summitEnd    int32  first + run_end[i]               count equals max
+ * with first = first_chromStart of the contig (one per CONTIG, NULL = zeros; the same 32-bit
+ * check as pack_segments).  Integer arithmetic only: the columns are the same whatever the
+ * schedule.  A solved set made from dense counts only (-1 and an error text otherwise).  Returns
+ * the total number of rows, -1 on failure; rows_out[p] (n_problems entries, host, may be NULL)
+ * receives problem p's row count.  The device addresses stay valid until the set is solved again
+ * or destroyed; ..._download copies the columns (any may be NULL) to host arrays of that many rows
+ * and returns -1 when the set has been solved again since the last pack call. */
+long long peakseg_hip_problem_set_pack_segment_stats(psd_problem_set *set, const int *first_chromStart,
+                                                     long long *rows_out, const long long **sum_dev,
+                                                     const int **max_dev, const int **summitStart_dev,
+                                                     const int **summitEnd_dev);
+int peakseg_hip_problem_set_packed_segment_stats_download(psd_problem_set *set, long long *sum_out,
+                                                          int *max_out, int *summitStart_out,
+                                                          int *summitEnd_out);
+/* the tile of that launch: runs one workgroup folds (tests aim at its boundaries) */
+int peakseg_hip_segment_stats_tile_runs(void);
+/* milliseconds (HIP events) of the calling thread's last pack_segment_stats: zeroing and launches */
+int peakseg_hip_segment_stats_last_ms(float *ms);
+
 /* The ten fields of the reference's loss.tsv row of one solved problem, in its order and with its
  * arithmetic: penalty, segments, peaks, bases, bedGraph.lines, mean.pen.cost, total.loss,
  * equality.constraints, mean.intervals, max.intervals.  0 or -1. */

@@ -181,6 +181,17 @@ def declare(lib):
     lib.peakseg_hip_dense_last_encode_ms.argtypes = [
         c.POINTER(c.c_float), c.POINTER(c.c_float), c.POINTER(c.c_float)]
     lib.peakseg_hip_dense_last_encode_ms.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_segment_stats.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p), c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_pack_segment_stats.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_segment_stats_download.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_problem_set_packed_segment_stats_download.restype = c.c_int
+    lib.peakseg_hip_segment_stats_tile_runs.argtypes = []
+    lib.peakseg_hip_segment_stats_tile_runs.restype = c.c_int
+    lib.peakseg_hip_segment_stats_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_segment_stats_last_ms.restype = c.c_int
     return lib
 
 
@@ -207,6 +218,9 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_packed_segments_download", "peakseg_hip_problem_set_loss",
     "peakseg_hip_dense_encode_probe", "peakseg_hip_dense_tile_bases",
     "peakseg_hip_dense_last_encode_ms",
+    "peakseg_hip_problem_set_pack_segment_stats",
+    "peakseg_hip_problem_set_packed_segment_stats_download",
+    "peakseg_hip_segment_stats_tile_runs", "peakseg_hip_segment_stats_last_ms",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -316,7 +316,8 @@ def _read_text_table(text, names):
                        float_precision="round_trip")
 
 
-def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=None, device=0):
+def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=None, device=0,
+                      stats=False):
     """PeakSegFPOP_vec without its files: dense integer coverage (one count per base) is
     run-length encoded and solved on the GPU, and the reference's result comes back as data
     frames.  count_vecs: one vector or a list of them (int32 numpy arrays or torch tensors are
@@ -325,7 +326,11 @@ def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=No
     the coordinate of each vector's first base (default 0).  Returns, for a single vector, a
     list over its penalties, else a list over vectors of such lists, of PeakSegFPOP_dir_result
     whose $segments and $loss are what PeakSegFPOP_dir reads from the files the file path
-    writes for the same runs (means pass through the files' "%g", penalties through paste())."""
+    writes for the same runs (means pass through the files' "%g", penalties through paste()).
+    stats=True: every result also gets .stats, a data frame with one row per row of .segments and
+    the columns reads (the sum of the segment's bases' counts), max.count, summitStart and
+    summitEnd (the first run of the segment whose count is max.count), computed on the GPU from
+    the resident runs (ProblemSet.segment_stats)."""
     from .grid import ProblemSet
     single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
         len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
@@ -382,6 +387,7 @@ def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=No
         except RuntimeError as e:
             raise PeakSegError(_native.ERROR_DEVICE_SOLVER, str(e))
         columns = pset.segment_columns(first_chromStart=chrom_starts)
+        seg_stats = pset.segment_stats(first_chromStart=chrom_starts) if stats else None
         rows = [(pset.loss(p), pset.result(p)) for p in range(len(problems))]
     finally:
         pset.close()
@@ -407,6 +413,9 @@ def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=No
         loss["seconds"] = float(seconds)
         flat.append(PeakSegFPOP_dir_result(
             _read_text_table(seg_text, col_name_list["segments"]), loss))
+        if stats:
+            flat[-1].stats = pd.DataFrame(dict(zip(
+                ["reads", "max.count", "summitStart", "summitEnd"], seg_stats[p])))
     out, o = [], 0
     for q in pens:
         out.append(flat[o:o + len(q)])

@@ -90,6 +90,8 @@
 
 /* run-length encoding of dense coverage and the reference's segments table, on the device */
 #include "dense_encode.h"
+/* reads, maximum and summit of every segment from the resident runs */
+#include "segment_stats.h"
 
 #include <ctype.h>
 #include <errno.h>
@@ -169,6 +171,8 @@ extern "C" void peakseg_hip_problem_set_destroy(psd_problem_set *s) {
   for (auto &e : s->ev)
     if (e) (void)hipEventDestroy(e);
   if (s->ev2) (void)hipEventDestroy(s->ev2);
+  for (auto &e : s->stats.ev)
+    if (e) (void)hipEventDestroy(e);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   if (s->stream2) (void)hipStreamDestroy(s->stream2);
   if (s->started) (void)hipHostFree(s->started);

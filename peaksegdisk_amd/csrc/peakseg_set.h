@@ -21,6 +21,7 @@ struct SolveRun {
   int parks = 0;                          /* problems parked by the last solve's launches */
   unsigned long long park_pool_pieces = 0; /* ... and what they took from the overflow pool */
   long long pack_total = -1, segs_total = -1; /* rows of the packed tables (-1: not packed) */
+  long long stats_total = -1;                 /* ... and of the packed segment statistics */
 };
 
 /* Segment tables packed at their exact sizes (peakseg_pack.h): up to three columns and, per
@@ -29,6 +30,21 @@ struct PackedTable {
   void *col[3] = {nullptr, nullptr, nullptr};
   long long *d_rows = nullptr;
   long long capacity = 0;
+};
+
+/* The four columns of peakseg_hip_problem_set_pack_segment_stats, the keys they are decoded from,
+ * and what the launches read: the per-problem descriptors (written by every call) and the problem
+ * of every tile of the grid (the set's geometry: made by the first call, kept) */
+struct StatsTable {
+  long long *sum = nullptr;
+  int *mx = nullptr, *summit_start = nullptr, *summit_end = nullptr;
+  unsigned long long *key = nullptr;
+  long long capacity = 0;
+  long long *d_desc = nullptr;
+  int *d_tile_problem = nullptr;
+  long long n_tiles = 0;
+  std::vector<long long> tile0; /* first tile of every problem */
+  hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 struct psd_problem_set {
@@ -92,6 +108,7 @@ struct psd_problem_set {
    * the reference's segments table (peakseg_hip_problem_set_pack_segments: chromStart, chromEnd,
    * mean) */
   PackedTable pack, segs;
+  StatsTable stats; /* (sets made from dense counts) */
 
   /* Sets made from dense counts (peakseg_hip_problem_set_create_dense): run_end[] next to count[]
    * and weight[], the sum of each contig's counts, and which contigs are constant.  Their trivial

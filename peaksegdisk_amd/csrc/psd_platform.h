@@ -169,6 +169,24 @@ PSD_D void agent_store_ptr(char **p, char *v) {
 }
 #endif
 
+/* 64-bit integer atomics on words in HBM that other workgroups of the launch update too; nothing
+ * is returned, so the device issues them and goes on */
+#ifdef PSD_EMU
+PSD_D void atomic_add_i64(long long *p, long long v) { (void)__atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+PSD_D void atomic_max_u64(unsigned long long *p, unsigned long long v) {
+  unsigned long long o = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v > o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+  }
+}
+#else
+PSD_D void atomic_add_i64(long long *p, long long v) {
+  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+PSD_D void atomic_max_u64(unsigned long long *p, unsigned long long v) {
+  (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif
+
 template <class T>
 PSD_D T *uniform_p(T *p) {
 #ifdef PSD_EMU

@@ -150,6 +150,46 @@ class ProblemSet:
         return [(start[offs[p]:offs[p + 1]], end[offs[p]:offs[p + 1]], mean[offs[p]:offs[p + 1]])
                 for p in range(k)]
 
+    def segment_stats(self, first_chromStart=None, torch_device=None):
+        """What every row of segment_columns() holds, computed on the device from the resident
+        runs (peakseg_hip_problem_set_pack_segment_stats), row for row in segment_columns()'
+        order: sum (int64, the reads under the segment: the sum of its bases' counts), max (int32,
+        its largest count), summitStart and summitEnd (int32, the coordinates of the first run in
+        genomic order whose count equals max).  first_chromStart as in segment_columns().
+        Without torch_device: a list over problems of (sum, max, summitStart, summitEnd) numpy
+        arrays.  With torch_device: (rows int64 numpy[k + 1], sum, max, summitStart, summitEnd)
+        where the four are tensors that alias the library's packed buffers: nothing is
+        downloaded, and they are valid until the next solve() / close()."""
+        k = len(self.problems)
+        rows = np.zeros(k, dtype=np.int64)
+        first = None
+        if first_chromStart is not None:
+            first = np.ascontiguousarray(first_chromStart, dtype=np.int32)
+            if first.shape != (len(self.contig_bases),):
+                raise ValueError("first_chromStart: one value per contig")
+        ptr = [ctypes.c_void_p() for _ in range(4)]
+        total = self._lib.peakseg_hip_problem_set_pack_segment_stats(
+            self._h, first.ctypes.data if first is not None else None, rows.ctypes.data,
+            *[ctypes.byref(q) for q in ptr])
+        if total < 0:
+            raise RuntimeError("pack_segment_stats: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        total = int(total)
+        offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+        dtypes = (np.int64, np.int32, np.int32, np.int32)
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            return (offs,) + tuple(device_array(q.value or 0, total, dt, dev)
+                                   for q, dt in zip(ptr, dtypes))
+        cols = [np.empty(total, dtype=dt) for dt in dtypes]
+        if self._lib.peakseg_hip_problem_set_packed_segment_stats_download(
+                self._h, *[a.ctypes.data for a in cols]) != 0:
+            raise RuntimeError("packed_segment_stats_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        return [tuple(a[offs[p]:offs[p + 1]] for a in cols) for p in range(k)]
+
     def loss(self, p):
         """The ten fields of the reference's loss.tsv row of problem p (api.col_name_list["loss"]),
         as float64."""

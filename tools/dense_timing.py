@@ -14,8 +14,15 @@
       host_encoded   numpy run-length encoding of the host vectors + ProblemSet + solve + a
                      segments call per problem
     The legs' results are compared for equality before any time is printed.
+(s) the segment statistics launch (peakseg_hip_problem_set_pack_segment_stats: zeroing, tile
+    kernel, finish kernel between two HIP events) on solved sets: the +Inf model of (a) once and
+    64 times in one set, the first 2.5e7 bases of (a) at four penalties, and set (b) with one
+    penalty per contig.  Warmed, --reps repetitions, minimum / median / maximum, next to the bytes
+    the launch must move (12 R per problem + 24 per row), that figure's share of the copy rate,
+    and the forward kernel's time for the same set.
 
 usage: python tools/dense_timing.py [--contigs 6144] [--reps 20] [--e2e-reps 2] [--skip-long]
+       [--skip-e2e] [--skip-stats]
 One JSON line per part on stdout."""
 import argparse
 import ctypes
@@ -42,6 +49,7 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--e2e-reps", type=int, default=2)
 ap.add_argument("--skip-long", action="store_true")
 ap.add_argument("--skip-e2e", action="store_true")
+ap.add_argument("--skip-stats", action="store_true")
 args = ap.parse_args()
 lib = _native.lib
 
@@ -82,11 +90,57 @@ def encoder_laps(tensors, reps):
             "bytes_per_s_best": traffic / (min(total) * 1e-3)}
 
 
+def stats_laps(part, tensors_, problems_, reps):
+    """one JSON line: the statistics launch on the solved set of `problems_`"""
+    s = ProblemSet.from_dense(tensors_, problems_)
+    try:
+        forward_ms = s.solve()[0]
+        k = len(problems_)
+        rows = np.zeros(k, np.int64)
+        ptr = [ctypes.c_void_p() for _ in range(4)]
+        laps = []
+        for rep in range(reps + 3):
+            total = lib.peakseg_hip_problem_set_pack_segment_stats(
+                s._h, None, rows.ctypes.data, *[ctypes.byref(q) for q in ptr])
+            assert total >= 0, _native.last_error()
+            ms = ctypes.c_float()
+            lib.peakseg_hip_segment_stats_last_ms(ctypes.byref(ms))
+            if rep >= 3:  # warmed
+                laps.append(ms.value)
+        runs = sum(int(s.loss(p)[4]) for p in range(k))
+        # the columns' sums against the contigs': the launch did its work
+        got = s.segment_stats()
+        sums = {}
+        for p, (c, _) in enumerate(problems_):
+            sums.setdefault(c, int(tensors_[c].sum(dtype=torch.int64)))
+            assert int(got[p][0].sum()) == sums[c], p
+        build = s.kernel_build
+    finally:
+        s.close()
+    med = statistics.median(laps)
+    must = 12.0 * runs + 24.0 * total
+    moved = 8.0 * runs + 64.0 * total
+    out = {"part": part, "problems": k, "runs_read": runs, "rows": int(total), "reps": reps,
+           "stats_ms": {"min": min(laps), "median": med, "max": max(laps)},
+           "bytes_12R_plus_24rows": must, "bytes_per_s_median": must / (med * 1e-3),
+           "share_of_copy_bandwidth": must / (med * 1e-3) / COPY_BW,
+           "bytes_8R_plus_64rows_the_launches_move": moved,
+           "forward_kernel_ms": forward_ms, "kernel_build": build,
+           "stats_share_of_forward": med / forward_ms if forward_ms > 0 else None}
+    print(json.dumps(out), flush=True)
+
+
 if not args.skip_long:
     cs, ce, cnt = synthetic.poisson_coverage(10 ** 7, seed=1)
     long_t = expand(cnt, (ce - cs).astype(np.int64))
     print(json.dumps(dict(part="a_encoder_one_contig", **encoder_laps([long_t], args.reps))),
           flush=True)
+    if not args.skip_stats:
+        inf = float("inf")
+        stats_laps("s_a_one_contig_inf_model", [long_t], [(0, inf)], args.reps)
+        stats_laps("s_a_one_contig_64_inf_models", [long_t], [(0, inf)] * 64, args.reps)
+        stats_laps("s_a_first_2.5e7_bases_4_penalties", [long_t[:25 * 10 ** 6]],
+                   [(0, 0.72), (0, 37.3), (0, 1550.5), (0, 51795.0)], args.reps)
     del long_t
     torch.cuda.empty_cache()
 
@@ -100,11 +154,13 @@ for k in range(args.contigs):
     tensors.append(expand(cnt, width))
 print(json.dumps(dict(part="b_encoder_many_contigs", **encoder_laps(tensors, args.reps))),
       flush=True)
+pens = [grid[k % 64] for k in range(args.contigs)]
+problems = [(k, float(pens[k])) for k in range(args.contigs)]
+if not args.skip_stats:
+    stats_laps("s_b_many_contigs_one_penalty_each", tensors, problems, args.reps)
 if args.skip_e2e:
     sys.exit(0)
 
-pens = [grid[k % 64] for k in range(args.contigs)]
-problems = [(k, float(pens[k])) for k in range(args.contigs)]
 host_vectors = [np.repeat(c, w).astype(np.int32) for c, w in bins]
 
 
