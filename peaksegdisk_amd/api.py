@@ -484,36 +484,19 @@ def PeakSegFPOP_dir_batch(problem_dirs, penalty_params, devices=None):
 
 # ---- sequentialSearch_dir (R/sequentialSearch_dir.R:22-103) --------------------------------
 
-def sequentialSearch_dir(problem_dir, peaks_int, verbose=0):
-    """The reference's penalty search for a target number of peaks.  The loop itself runs in
-    the native library (PeakSegFPOP_sequential_search: coverage.bedGraph parsed and uploaded
-    once, arena reused from one penalty to the next); it visits the reference's penalties and
-    leaves the reference's files, from which the result is assembled here."""
-    import ctypes
-    if not (isinstance(peaks_int, (int, np.integer)) and not isinstance(peaks_int, bool)
-            and 0 <= peaks_int):
-        raise ValueError("is.integer(peaks.int) && length(peaks.int) == 1 && 0 <= peaks.int "
-                         "is not TRUE")
-    if not isinstance(problem_dir, str):
-        raise ValueError("is.character(problem.dir) is not TRUE")
-    cap = 256
-    rows = (_native.PsdSearchRow * cap)()
-    n_rows = ctypes.c_int(0)
-    chosen = ctypes.c_int(-1)
-    st = _native.lib.PeakSegFPOP_sequential_search(
-        os.fsencode(problem_dir), int(peaks_int), int(bool(verbose)), cap, rows,
-        ctypes.byref(n_rows), ctypes.byref(chosen))
-    if st == _native.ERROR_SEARCH_TOO_MANY_PEAKS:
-        raise ValueError(_native.last_error())
-    if st != 0:
-        bg = os.path.realpath(os.path.join(problem_dir, "coverage.bedGraph"))
-        pen = rows[n_rows.value].penalty_str.decode() if n_rows.value < cap else ""
-        msg = _native.status_message(st, bg, pen, "%s_penalty=%s.db" % (bg, pen))
-        detail = _native.last_error()
-        if st >= _native.ERROR_NO_HIP_DEVICE and detail:
-            msg = "%s (%s)" % (msg, detail)
-        raise PeakSegError(st, msg)
-    return _search_result(problem_dir, [rows[k] for k in range(n_rows.value)], chosen.value)
+def _check_peaks(peaks_int, n_dirs=None):
+    """peaks.int of the search wrappers: one non-negative integer (n_dirs None), or one for all
+    of n_dirs directories or one per directory -> list"""
+    scalar = isinstance(peaks_int, (int, np.integer)) and not isinstance(peaks_int, bool)
+    if n_dirs is None:
+        if not (scalar and 0 <= peaks_int):
+            raise ValueError("is.integer(peaks.int) && length(peaks.int) == 1 && 0 <= peaks.int "
+                             "is not TRUE")
+        return int(peaks_int)
+    peaks = [int(peaks_int)] * n_dirs if scalar else [int(p) for p in peaks_int]
+    if len(peaks) != n_dirs or any(p < 0 for p in peaks):
+        raise ValueError("peaks.int: one non-negative integer, or one per problem directory")
+    return peaks
 
 
 def _search_result(problem_dir, rows, chosen):
@@ -533,6 +516,69 @@ def _search_result(problem_dir, rows, chosen):
     return out
 
 
+def _search_outcome(status, rows, n_rows, chosen, problem_dir, with_detail):
+    """What a native search left for one directory -> its result, or the exception of its failure.
+    rows[n_rows] names the model that failed (the table is full: no name)."""
+    if status == _native.ERROR_SEARCH_TOO_MANY_PEAKS:
+        raise ValueError(_native.last_error())
+    if status != 0:
+        bg = os.path.realpath(os.path.join(problem_dir, "coverage.bedGraph"))
+        pen = rows[n_rows].penalty_str.decode() if n_rows < len(rows) else ""
+        msg = _native.status_message(status, bg, pen, "%s_penalty=%s.db" % (bg, pen))
+        detail = _native.last_error()
+        if with_detail and status >= _native.ERROR_NO_HIP_DEVICE and detail:
+            msg = "%s (%s)" % (msg, detail)
+        raise PeakSegError(status, msg)
+    return _search_result(problem_dir, rows[:n_rows], chosen)
+
+
+def _search_one(problem_dir, peaks_int, cap, call):
+    """A single-directory search: call(dir, peaks, cap, rows, n_rows, chosen) -> status"""
+    import ctypes
+    peaks_int = _check_peaks(peaks_int)
+    if not isinstance(problem_dir, str):
+        raise ValueError("is.character(problem.dir) is not TRUE")
+    rows = (_native.PsdSearchRow * cap)()
+    n_rows = ctypes.c_int(0)
+    chosen = ctypes.c_int(-1)
+    st = call(os.fsencode(problem_dir), peaks_int, cap, rows, ctypes.byref(n_rows),
+              ctypes.byref(chosen))
+    return _search_outcome(st, rows, n_rows.value, chosen.value, problem_dir, True)
+
+
+def _search_many(problem_dirs, peaks_int, cap, devices, call):
+    """A lockstep search: call(n, dirs, peaks, cap, rows, n_rows, chosen, status); a failed search
+    raises for the first failure"""
+    import ctypes
+    problem_dirs = list(problem_dirs)
+    n = len(problem_dirs)
+    peaks_int = _check_peaks(peaks_int, n)
+    if not all(isinstance(d, str) for d in problem_dirs):
+        raise ValueError("is.character(problem.dir) is not TRUE")
+    if n == 0:
+        return []
+    rows = (_native.PsdSearchRow * (cap * n))()
+    dirs = (ctypes.c_char_p * n)(*[os.fsencode(d) for d in problem_dirs])
+    peaks = (ctypes.c_int * n)(*peaks_int)
+    n_rows = (ctypes.c_int * n)()
+    chosen = (ctypes.c_int * n)()
+    status = (ctypes.c_int * n)()
+    with _devices_knob(devices):
+        call(n, dirs, peaks, cap, rows, n_rows, chosen, status)
+    return [_search_outcome(status[d], rows[d * cap:(d + 1) * cap], n_rows[d], chosen[d],
+                            problem_dirs[d], False) for d in range(n)]
+
+
+def sequentialSearch_dir(problem_dir, peaks_int, verbose=0):
+    """The reference's penalty search for a target number of peaks.  The loop itself runs in
+    the native library (PeakSegFPOP_sequential_search: coverage.bedGraph parsed and uploaded
+    once, arena reused from one penalty to the next); it visits the reference's penalties and
+    leaves the reference's files, from which the result is assembled here."""
+    return _search_one(
+        problem_dir, peaks_int, 256, lambda d, peaks, cap, *out:
+        _native.lib.PeakSegFPOP_sequential_search(d, peaks, int(bool(verbose)), cap, *out))
+
+
 def sequentialSearch_dir_batch(problem_dirs, peaks_int, verbose=0, devices=None):
     """sequentialSearch_dir over several problem directories at once (additive): each directory
     gets the result sequentialSearch_dir(dir, peaks) gives, but the models the searches ask for
@@ -541,41 +587,10 @@ def sequentialSearch_dir_batch(problem_dirs, peaks_int, verbose=0, devices=None)
     directory.  devices: "all" or device ids -- the directories dealt to one shard per listed
     device (PEAKSEG_HIP_DEVICES for this call; None: the environment decides).  Returns the
     list of results; a failed search raises for the first failure."""
-    import ctypes
-    problem_dirs = list(problem_dirs)
-    n = len(problem_dirs)
-    if isinstance(peaks_int, (int, np.integer)) and not isinstance(peaks_int, bool):
-        peaks_int = [int(peaks_int)] * n
-    peaks_int = [int(p) for p in peaks_int]
-    if len(peaks_int) != n or any(p < 0 for p in peaks_int):
-        raise ValueError("peaks.int: one non-negative integer, or one per problem directory")
-    if not all(isinstance(d, str) for d in problem_dirs):
-        raise ValueError("is.character(problem.dir) is not TRUE")
-    if n == 0:
-        return []
-    cap = 256
-    rows = (_native.PsdSearchRow * (cap * n))()
-    dirs = (ctypes.c_char_p * n)(*[os.fsencode(d) for d in problem_dirs])
-    peaks = (ctypes.c_int * n)(*peaks_int)
-    n_rows = (ctypes.c_int * n)()
-    chosen = (ctypes.c_int * n)()
-    status = (ctypes.c_int * n)()
-    with _devices_knob(devices):
+    return _search_many(
+        problem_dirs, peaks_int, 256, devices, lambda n, dirs, peaks, cap, *out:
         _native.lib.PeakSegFPOP_sequential_search_batch(n, dirs, peaks, int(bool(verbose)), cap,
-                                                        rows, n_rows, chosen, status)
-    out = []
-    for d in range(n):
-        if status[d] == _native.ERROR_SEARCH_TOO_MANY_PEAKS:
-            raise ValueError(_native.last_error())
-        if status[d] != 0:
-            bg = os.path.realpath(os.path.join(problem_dirs[d], "coverage.bedGraph"))
-            k = n_rows[d]
-            pen = rows[d * cap + k].penalty_str.decode() if k < cap else ""
-            raise PeakSegError(status[d], _native.status_message(
-                status[d], bg, pen, "%s_penalty=%s.db" % (bg, pen)))
-        out.append(_search_result(problem_dirs[d],
-                                  [rows[d * cap + k] for k in range(n_rows[d])], chosen[d]))
-    return out
+                                                        *out))
 
 
 # ---- the parallel penalty search (additive; DESIGN.md section 8) ----------------------------
@@ -598,33 +613,11 @@ def parallelSearch_dir(problem_dir, peaks_int, width=None, verbose=0, devices=No
     devices: "all" or device ids -- each round's models dealt over the listed devices
     (PEAKSEG_HIP_DEVICES for this call; None: the environment decides).  Same result shape as
     sequentialSearch_dir: $others has one row per model, `iteration` is the round."""
-    import ctypes
-    if not (isinstance(peaks_int, (int, np.integer)) and not isinstance(peaks_int, bool)
-            and 0 <= peaks_int):
-        raise ValueError("is.integer(peaks.int) && length(peaks.int) == 1 && 0 <= peaks.int "
-                         "is not TRUE")
-    if not isinstance(problem_dir, str):
-        raise ValueError("is.character(problem.dir) is not TRUE")
-    width = _check_width(width)
-    cap = 1024
-    rows = (_native.PsdSearchRow * cap)()
-    n_rows = ctypes.c_int(0)
-    chosen = ctypes.c_int(-1)
-    with _devices_knob(devices):
-        st = _native.lib.PeakSegFPOP_parallel_search(
-            os.fsencode(problem_dir), int(peaks_int), width, int(bool(verbose)), cap, rows,
-            ctypes.byref(n_rows), ctypes.byref(chosen))
-    if st == _native.ERROR_SEARCH_TOO_MANY_PEAKS:
-        raise ValueError(_native.last_error())
-    if st != 0:
-        bg = os.path.realpath(os.path.join(problem_dir, "coverage.bedGraph"))
-        pen = rows[n_rows.value].penalty_str.decode() if n_rows.value < cap else ""
-        msg = _native.status_message(st, bg, pen, "%s_penalty=%s.db" % (bg, pen))
-        detail = _native.last_error()
-        if st >= _native.ERROR_NO_HIP_DEVICE and detail:
-            msg = "%s (%s)" % (msg, detail)
-        raise PeakSegError(st, msg)
-    return _search_result(problem_dir, [rows[k] for k in range(n_rows.value)], chosen.value)
+    def call(d, peaks, cap, *out):
+        with _devices_knob(devices):
+            return _native.lib.PeakSegFPOP_parallel_search(d, peaks, _check_width(width),
+                                                           int(bool(verbose)), cap, *out)
+    return _search_one(problem_dir, peaks_int, 1024, call)
 
 
 def parallelSearch_dir_batch(problem_dirs, peaks_int, width=None, verbose=0, devices=None):
@@ -634,39 +627,8 @@ def parallelSearch_dir_batch(problem_dirs, peaks_int, width=None, verbose=0, dev
     target for all, or one per directory.  devices: "all" or device ids -- the directories dealt
     to one shard per listed device.  Returns the list of results; a failed search raises for the
     first failure."""
-    import ctypes
-    problem_dirs = list(problem_dirs)
-    n = len(problem_dirs)
-    if isinstance(peaks_int, (int, np.integer)) and not isinstance(peaks_int, bool):
-        peaks_int = [int(peaks_int)] * n
-    peaks_int = [int(p) for p in peaks_int]
-    if len(peaks_int) != n or any(p < 0 for p in peaks_int):
-        raise ValueError("peaks.int: one non-negative integer, or one per problem directory")
-    if not all(isinstance(d, str) for d in problem_dirs):
-        raise ValueError("is.character(problem.dir) is not TRUE")
     width = _check_width(width)
-    if n == 0:
-        return []
-    cap = 1024
-    rows = (_native.PsdSearchRow * (cap * n))()
-    dirs = (ctypes.c_char_p * n)(*[os.fsencode(d) for d in problem_dirs])
-    peaks = (ctypes.c_int * n)(*peaks_int)
-    n_rows = (ctypes.c_int * n)()
-    chosen = (ctypes.c_int * n)()
-    status = (ctypes.c_int * n)()
-    with _devices_knob(devices):
+    return _search_many(
+        problem_dirs, peaks_int, 1024, devices, lambda n, dirs, peaks, cap, *out:
         _native.lib.PeakSegFPOP_parallel_search_batch(n, dirs, peaks, width, int(bool(verbose)),
-                                                      cap, rows, n_rows, chosen, status)
-    out = []
-    for d in range(n):
-        if status[d] == _native.ERROR_SEARCH_TOO_MANY_PEAKS:
-            raise ValueError(_native.last_error())
-        if status[d] != 0:
-            bg = os.path.realpath(os.path.join(problem_dirs[d], "coverage.bedGraph"))
-            k = n_rows[d]
-            pen = rows[d * cap + k].penalty_str.decode() if k < cap else ""
-            raise PeakSegError(status[d], _native.status_message(
-                status[d], bg, pen, "%s_penalty=%s.db" % (bg, pen)))
-        out.append(_search_result(problem_dirs[d],
-                                  [rows[d * cap + k] for k in range(n_rows[d])], chosen[d]))
-    return out
+                                                      cap, *out))

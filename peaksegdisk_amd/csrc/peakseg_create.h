@@ -4,7 +4,7 @@ namespace {
 
 /* PEAKSEG_HIP_TIMING=1: where the creation of a set spends its time, on stderr */
 struct CreateLaps {
-  bool on = getenv("PEAKSEG_HIP_TIMING") != nullptr;
+  bool on = timing_on();
   std::chrono::steady_clock::time_point mark = std::chrono::steady_clock::now();
   void operator()(const char *what) {
     if (!on) return;

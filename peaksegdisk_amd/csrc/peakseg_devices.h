@@ -1,5 +1,5 @@
 /* peakseg_devices.h -- which GPU a call uses, and the per-thread state of a call fanned out over
- * several (PEAKSEG_HIP_DEVICES; the fan-out itself is in peakseg_files.h). */
+ * several (PEAKSEG_HIP_DEVICES; the fan-out itself is in peakseg_fanout.h). */
 namespace {
 
 /* A shard thread of a fanned-out call: the device it is pinned to (-1 elsewhere).  Its nested

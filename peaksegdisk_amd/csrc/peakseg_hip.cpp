@@ -8,7 +8,8 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, files), each headed by what it holds.
+ * per concern (text, set, devices, create, solve, pack, dense, fanout, files, dir, search), each
+ * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
  * (tests/emu builds the same file with g++ -DPSD_EMU against the SIMT emulator).
@@ -440,9 +441,12 @@ extern "C" int peakseg_hip_problem_set_max_spin(psd_problem_set *s, int p) {
   return s->results[(size_t)p].max_spin;
 }
 
-/* ---- file-level solver (the reference's boundary), directory-level batch with the cache
- *      protocol, resident penalty search ----------------------------------------------------- */
+/* ---- the dynamic programs of a call on the devices, the file-level solver (the reference's
+ *      boundary), the directory-level batch with the cache protocol, the penalty searches ------ */
+#include "peakseg_fanout.h"
 #include "peakseg_files.h"
+#include "peakseg_dir.h"
+#include "peakseg_search.h"
 
 extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, const char *penalty,
                                             const char *db, char *buf, size_t buf_len) {

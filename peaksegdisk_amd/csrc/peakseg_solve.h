@@ -65,7 +65,7 @@ struct PlanKnobs {
    * an MI355X at 2.4 GHz */
   double lat_rate = g_lat_rate.load(), thr_rate = g_thr_rate.load();
   bool no_packed = getenv("PEAKSEG_HIP_NO_PACKED") || g_pk_handed_over_many.load();
-  bool timing = getenv("PEAKSEG_HIP_TIMING") != nullptr;
+  bool timing = timing_on();
   PlanKnobs() {
     if (const char *e = getenv("PEAKSEG_HIP_RATES")) { /* diagnostic: "lat,thr" data points per s */
       double a = 0.0, b = 0.0;
@@ -211,7 +211,7 @@ int enqueue_mixed(psd_problem_set *s, Build rest_build, const int *d_order, int 
   }
   enqueue_forward(s, rest_build, s->stream, d_thr);
   HIP_TRY(hipGetLastError());
-  if (getenv("PEAKSEG_HIP_TIMING") && !*ev_packed_end && hipEventCreate(ev_packed_end) != hipSuccess)
+  if (timing_on() && !*ev_packed_end && hipEventCreate(ev_packed_end) != hipSuccess)
     *ev_packed_end = nullptr;
   if (*ev_packed_end) HIP_TRY(hipEventRecord(*ev_packed_end, s->stream));
   HIP_TRY(hipEventRecord(s->ev2, s->stream2));
@@ -546,7 +546,7 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
     Unfinished u;
     if ((st = collect(s, todo, u))) return st;
     if (u.again.empty()) break;
-    if (getenv("PEAKSEG_HIP_TIMING")) {
+    if (timing_on()) {
       fprintf(stderr, "peakseg_hip timing: launch %d: %d of %d problems unfinished (arena %d, spill "
                       "pool %d, checkpoint pool %d, to wider lists %d):", s->run.launches,
               (int)u.again.size(), n_todo, (int)u.arena_full, (int)u.spill_full, (int)u.ckpt_full,

@@ -1,6 +1,16 @@
-/* peakseg_text.h -- what the host driver says and reads as text: last error and warning, printing
- * through R's or the shards' channel, HIP_TRY, the reference's bedGraph and penalty parsing. */
+/* peakseg_text.h -- what the host driver says and reads as text: last error and warning, the
+ * PEAKSEG_HIP_TIMING switch and its clock, printing through R's or the shards' channel, HIP_TRY,
+ * the reference's bedGraph and penalty parsing, R's paste() of a double. */
 namespace {
+
+/* PEAKSEG_HIP_TIMING=1: where a call spends its time, on stderr */
+bool timing_on() { return getenv("PEAKSEG_HIP_TIMING") != nullptr; }
+
+double wall_now() {
+  struct timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
 
 thread_local std::string g_last_error;
 void (*g_print)(const char *) = nullptr;
@@ -24,7 +34,7 @@ void set_warning(const char *fmt, ...) {
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
   g_last_warning = buf;
-  if (getenv("PEAKSEG_HIP_TIMING")) fprintf(stderr, "peakseg_hip warning: %s\n", buf);
+  if (timing_on()) fprintf(stderr, "peakseg_hip warning: %s\n", buf);
 }
 
 void print_text(const char *text) {
@@ -240,4 +250,56 @@ int parse_penalty(const char *s, bool &is_Inf, double &penalty) {
   return 0;
 }
 
+/* R's paste()/as.character() of a double: 15 significant digits, trailing zeros dropped, the
+ * narrower of fixed and scientific notation (R's formatReal with digits = 15).  The penalties
+ * of sequentialSearch_dir reach the solver and the file names through this
+ * (R/sequentialSearch_dir.R:43, R/PeakSegFPOP_dir.R:64), and write.table() formats
+ * _timing.tsv the same way (R/PeakSegFPOP_dir.R:102-106). */
+std::string r_paste_double(double x) {
+  if (x != x) return "NaN";
+  if (std::isinf(x)) return x > 0 ? "Inf" : "-Inf";
+  if (x == 0) return "0";
+  char buf[64];
+  snprintf(buf, sizeof buf, "%.14e", x);
+  const double target = strtod(buf, nullptr);
+  int nsig = 15;
+  for (int d = 1; d <= 15; d++) { /* fewest digits that reproduce the 15-digit value */
+    snprintf(buf, sizeof buf, "%.*e", d - 1, x);
+    if (strtod(buf, nullptr) == target) {
+      nsig = d;
+      break;
+    }
+  }
+  snprintf(buf, sizeof buf, "%.*e", nsig - 1, x);
+  const char *e = strchr(buf, 'e');
+  const int kpower = e ? atoi(e + 1) : 0;
+  const int neg = x < 0 ? 1 : 0;
+  int left, rgt;
+  if (kpower >= 0) {
+    left = kpower + 1;
+    rgt = nsig - kpower - 1;
+    if (rgt < 0) rgt = 0;
+  } else {
+    left = 1;
+    rgt = nsig - kpower - 1;
+  }
+  const int w_fixed = neg + left + (rgt > 0 ? rgt + 1 : 0);
+  const int w_sci = neg + (nsig > 1 ? nsig + 1 : 1) + (abs(kpower) >= 100 ? 5 : 4);
+  char out[400];
+  if (w_fixed <= w_sci) {
+    snprintf(out, sizeof out, "%.*f", rgt, x);
+  } else {
+    snprintf(out, sizeof out, "%.*e", nsig - 1, x);
+  }
+  return out;
+}
+
 }  // namespace
+
+/* Tests: R's paste() of a double as this library formats penalties and timing files. */
+extern "C" int peakseg_hip_paste_double(double x, char *buf, size_t buf_len) {
+  std::string s = r_paste_double(x);
+  if (!buf || buf_len == 0) return (int)s.size();
+  snprintf(buf, buf_len, "%s", s.c_str());
+  return (int)s.size();
+}
