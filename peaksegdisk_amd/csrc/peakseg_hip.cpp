@@ -32,12 +32,8 @@
 #define PSD_VARIANT lat
 #define PSD_LDS_CAP 128
 #define PSD_MATH_VK 1
-#ifndef PSD_NO_HELPER_WAVES /* -DPSD_NO_HELPER_WAVES: A/B builds (tools/ab_libs.py) */
 #define PSD_HELPER_WAVES 1
-#endif
-#ifndef PSD_NO_FLAG_BARRIER /* -DPSD_NO_FLAG_BARRIER: A/B builds */
 #define PSD_FLAG_BARRIER 1
-#endif
 #include "fpop_kernels.h"
 #undef PSD_VARIANT
 #undef PSD_LDS_CAP
@@ -53,21 +49,12 @@
 #endif
 #define PSD_LDS_CAP PSD_THR_LDS_CAP
 #define PSD_KERNEL_WAVES_PER_EU PSD_THR_WAVES_PER_EU
-#ifdef PSD_THR_FLAG_BARRIER /* A/B: measured slower than the workgroup barrier */
-#define PSD_FLAG_BARRIER 1
-#endif
-#if !defined(PSD_CALL_LDS_OPS) && !defined(PSD_THR_INLINE_OPS) /* A/B: -DPSD_THR_INLINE_OPS */
 #define PSD_CALL_LDS_OPS 1
-#define PSD_CALL_LDS_OPS_THR_ONLY 1
-#endif
 #include "fpop_kernels.h"
 #undef PSD_VARIANT
 #undef PSD_LDS_CAP
 #undef PSD_KERNEL_WAVES_PER_EU
-#ifdef PSD_CALL_LDS_OPS_THR_ONLY
 #undef PSD_CALL_LDS_OPS
-#undef PSD_CALL_LDS_OPS_THR_ONLY
-#endif
 
 /*   pk   packed build (round 4): 40 pieces per LDS list, registers for three waves per SIMD
  *        (six workgroups per CU), operations out of line.  A problem on a SIMD shared three ways

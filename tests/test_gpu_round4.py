@@ -171,7 +171,7 @@ def test_parked_long_functions_survive_several_exhaustions(psd, oracle_det, tmp_
 def test_spin_bounds_leave_three_orders_of_magnitude(psd, tmp_path, n_bins=30000):
     """The waves of a workgroup meet through LDS flags (step_sync, the helper mailboxes) with a
     bound on the number of polls, so that a lost wave becomes an error status instead of a hang
-    (fpop_kernels.h SPIN_LIMIT, fpop_wave.h MAIL_SPIN_LIMIT: 2^26 polls).  The bound must never
+    (fpop_sync.h SPIN_LIMIT, fpop_lds.h MAIL_SPIN_LIMIT: 2^26 polls).  The bound must never
     be reached by a wave that is merely slow.  A build with -DPSD_SPIN_STATS records the largest
     poll count of every wait; on the slowest legitimate steps there are -- lists in HBM,
     functions of several hundred pieces, chunk 0's Newton solves running to their 100-step cap

@@ -47,7 +47,7 @@ PHASES = [
     ("loop top", "fpop_kernels.h forward_body", [
         ("lds_round_trip", 1, "n[] of the two input functions"),
         ("div", 1, "penalty / cum_weight_prev (par: under the round trip)", "par")]),
-    ("first pass (piece costs, classes)", "fpop_wave.h piece_costs_wave, min_*_pre", [
+    ("first pass (piece costs, classes)", "fpop_walks.h piece_costs_wave, min_*_pre", [
         ("lds_round_trip", 1, "coefficients and ends of piece i"),
         ("div", 1, "argmin_mean = -Log/Linear"),
         ("log", 1, "exp(mn) | exp(mx) | log(argmin_mean) interleaved: the log is the longest"),
@@ -56,29 +56,29 @@ PHASES = [
         ("lds_round_trip", 1, "neighbour's left cost for the class of piece i"),
         ("fma", 6, "class decision"),
         ("exec_region", 3, "")]),
-    ("speculation round", "fpop_wave.h min_less_impl / min_more_impl", [
+    ("speculation round", "fpop_walks.h min_less_impl / min_more_impl", [
         ("fma", 10, "task lane -> (start, piece): integer division by the window"),
         ("lds_round_trip", 1, "level, piece, optimum, end costs of the pair"),
         ("fma", 4, "has_two_roots"),
         ("NEWTON_SPEC", 1, "wave-level trips x cycles per trip"),
         ("ballot", 3, "event / inside / bad masks"),
         ("exec_region", 3, "")]),
-    ("walk (state machine)", "fpop_wave.h min_*_impl", [
+    ("walk (state machine)", "fpop_walks.h min_*_impl", [
         ("WALK_ROUNDS", 1, "rounds x (search ballot, 8 readlane pairs, event look-up, 3 uniform "
                            "branches, 12 predicated updates)"),
         ("ballot", 2, "emission masks"),
         ("lds_store_issue", 14, "one parallel pass: two pieces of 7 fields per lane"),
         ("exec_region", 2, "")]),
-    ("interval table", "fpop_wave.h min_env_impl", [
+    ("interval table", "fpop_envelope.h min_env_impl", [
         ("lds_round_trip", 1, "own end x"),
         ("TABLE_ENDS", 1, "(n1 + n2) broadcast ends x (readlane pair, compare, add)"),
         ("lds_round_trip", 1, "duplicate test against the other list's end"),
         ("ballot", 2, ""), ("lds_store_issue", 1, "")]),
-    ("interval loads", "fpop_wave.h env_load_interval, env_neighbour_flags", [
+    ("interval loads", "fpop_envelope.h env_load_interval, env_neighbour_flags", [
         ("lds_round_trip", 1, "iv(k)"),
         ("lds_round_trip", 1, "the two pieces of the interval"),
         ("fma", 6, "same_funs, interval ends"), ("ballot", 1, "")]),
-    ("classification", "fpop_wave.h env_classify_lanes + helper_root_lanes", [
+    ("classification", "fpop_envelope.h env_classify_lanes + fpop_coop.h helper_root_lanes", [
         ("lds_store_issue", 6, "difference piece to the mailbox"),
         ("CLASSIFY", 1, "max(chain wave: exp|exp, log|log, exp|exp, costs, smaller-root trips, "
                         "early tail exp-log-exp; helper: wake-up, mailbox read, log, exp, "
@@ -88,18 +88,18 @@ PHASES = [
         ("REDO", 1, "exp-log-exp again when the larger root is the first crossing (share of steps)"),
         ("fma", 20, "decisions (selects)"),
         ("exec_region", 6, "")]),
-    ("compaction", "fpop_wave.h min_env_impl", [
+    ("compaction", "fpop_envelope.h min_env_impl", [
         ("ballot", 3, ""), ("bpermute", 1, "predecessor's identity"),
         ("lds_round_trip", 1, "predecessor's fields"),
         ("fma", 6, "coalescing tests"), ("ballot", 3, "heads"),
         ("lds_store_issue", 21, "up to three pieces of 7 fields"),
         ("ballot", 1, "run ends"), ("exec_region", 4, "")]),
-    ("rescale + arena record", "fpop_kernels.h scale_add_store_wave", [
+    ("rescale + arena record", "fpop_arena.h scale_add_store_wave", [
         ("div", 1, "1 / cum_weight"),
         ("lds_round_trip", 1, "the function and the cursor's addresses"),
         ("fma", 3, "multiply, add, multiply"),
         ("lds_store_issue", 6, "3 to LDS, 3 to HBM (not waited for)")]),
-    ("end of the data point", "fpop_kernels.h step_sync", [
+    ("end of the data point", "fpop_sync.h step_sync", [
         ("lds_round_trip", 1, "the other wave's arrival flag (it is there already in the floor)"),
         ("lds_round_trip", 1, "abort status")]),
 ]
