@@ -36,6 +36,11 @@ extern "C" {
 #define ERROR_DENSE_ARGUMENTS 17   /* dense counts that cannot be solved: 2^31 or more bases, a
                                       negative count, counts that sum to 2^53 or more, 2^30 or more
                                       runs; the contig and the reason are in peakseg_hip_last_error() */
+#define ERROR_READS_ARGUMENTS 18   /* aligned reads that cannot be piled up: an empty or negative
+                                      extent, bases_counted not 0/1, a NULL or misaligned array, a
+                                      read with chromStart >= chromEnd or a negative count, counts
+                                      that sum to 2^31 or more in a contig; the contig, the read and
+                                      the reason are in peakseg_hip_last_error() */
 
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
@@ -78,7 +83,8 @@ extern "C" {
  *                               assumes for the latency / throughput build (default: measured by
  *                               this process's earlier solves, else 96000,58000)
  * PEAKSEG_HIP_TIMING=1          phase timings of the file-level calls and of the creation of a
- *                               problem set (the dense encoder's launches included) on stderr */
+ *                               problem set (the pile-up of reads and the dense encoder's launches included) on
+ *                               stderr */
 
 /* ---- the reference's boundary -------------------------------------------------------- */
 
@@ -266,6 +272,35 @@ int peakseg_hip_problem_set_create_dense(int device, int n_contigs,
                                          const double *problem_penalty,
                                          unsigned long long arena_pieces, psd_problem_set **out);
 
+/* The same set from ALIGNED READS: contig c has n_reads[c] reads, read i covering the bases
+ * [read_start[c][i], read_end[c][i]) read_count[c][i] times (read_count NULL, or NULL for a contig:
+ * every read counts 1), in any order.  The coverage of the contig's extent
+ * [extent_start[c], extent_end[c]) is piled up on the device -- +count where a read starts, -count
+ * where it ends, prefix sum; four launches per call however many contigs it has -- into a buffer
+ * of one int32 per base, which the dense encoder reads in place and which is freed when the
+ * encoding ends.  bases_counted = 0: every base of a read counts; 1: only its last base
+ * (the interval [end - 1, end)).  A read is clipped to the extent; one that misses it adds nothing;
+ * a contig with no read inside its extent has all-zero coverage (the one-segment model).
+ * reads_on_device = 0: the arrays are host arrays, uploaded; 1: device addresses (multiples of 4) on
+ * `device`, read in place by launches on the null stream and not referred to after the call.
+ * From the encoder on the set is one of peakseg_hip_problem_set_create_dense, with base 0 of contig
+ * c at extent_start[c]: pass that as first_chromStart for genomic coordinates.
+ * Checks, in this order: penalties (as above); n_contigs <= 0: ERROR_NO_DATA; what the host sees --
+ * extent_end <= extent_start, extent_start < 0, bases_counted not 0/1, a NULL array where
+ * n_reads > 0, n_reads < 0, a device address that is no multiple of 4: ERROR_READS_ARGUMENTS; the
+ * device: ERROR_NO_HIP_DEVICE; what the pile-up finds -- a read with start >= end or a negative
+ * count (the first such read of the contig is named), good reads' counts that sum to 2^31 or more
+ * in a contig (a coverage value could overflow; reads outside the extent count too):
+ * ERROR_READS_ARGUMENTS, and nothing further is launched; then what the encoder refuses
+ * (ERROR_DENSE_ARGUMENTS). */
+int peakseg_hip_problem_set_create_reads(int device, int n_contigs, const long long *n_reads,
+                                         const int *const *read_start, const int *const *read_end,
+                                         const int *const *read_count, int reads_on_device,
+                                         const int *extent_start, const int *extent_end,
+                                         int bases_counted, int n_problems, const int *problem_contig,
+                                         const double *problem_penalty,
+                                         unsigned long long arena_pieces, psd_problem_set **out);
+
 /* Run forward DP + backtrack for every problem of the set; inputs are already resident.
  * *forward_ms = duration of the kernel, measured with HIP events on the stream it runs on.
  * Each workgroup decodes its segmentation right after its last data point, inside the same
@@ -420,6 +455,21 @@ int peakseg_hip_dense_encode_probe(int device, int n_contigs, const long long *n
 int peakseg_hip_dense_tile_bases(void);
 /* milliseconds (HIP events) of the three launches of the calling thread's last encoding */
 int peakseg_hip_dense_last_encode_ms(float *count_ms, float *scan_ms, float *scatter_ms);
+
+/* Tests and coverage_from_reads: the pile-up alone, and the encoding of it when any of runs_out /
+ * count_out / weight_out / run_end_out is given.  The read arguments as
+ * peakseg_hip_problem_set_create_reads; coverage_out (host, the sum of the extents' bases, or NULL)
+ * receives the contigs' coverage one after the other, the other four what
+ * peakseg_hip_dense_encode_probe gives.  Statuses as the creator's, without the penalties. */
+int peakseg_hip_reads_pileup_probe(int device, int n_contigs, const long long *n_reads,
+                                   const int *const *read_start, const int *const *read_end,
+                                   const int *const *read_count, int reads_on_device,
+                                   const int *extent_start, const int *extent_end, int bases_counted,
+                                   int *coverage_out, long long *runs_out, int *count_out,
+                                   int *weight_out, int *run_end_out);
+/* milliseconds (HIP events) of the calling thread's last pile-up: zeroing and scatter_kernel; the
+ * three launches of the prefix sum */
+int peakseg_hip_reads_last_pileup_ms(float *scatter_ms, float *scan_ms);
 
 /* Tests: R's paste() of a double (15 significant digits) as the penalty search and the timing
  * files format numbers; returns the length. */

@@ -6,14 +6,15 @@ behind the reference's own entry points.  See DESIGN.md and INTEGRATION.md.
 """
 from . import _native  # noqa: F401  (fails loudly when the HIP library is not built)
 from .api import (PeakSegError, PeakSegFPOP_dir, PeakSegFPOP_df, PeakSegFPOP_file,  # noqa: F401
-                  PeakSegFPOP_vec, PeakSegFPOP_dense, PeakSegFPOP_dir_batch, col_name_list, paste,
+                  PeakSegFPOP_vec, PeakSegFPOP_dense, PeakSegFPOP_reads, coverage_from_reads,
+                  PeakSegFPOP_dir_batch, col_name_list, paste,
                   sequentialSearch_dir, sequentialSearch_dir_batch, parallelSearch_dir,
                   parallelSearch_dir_batch, writeBedGraph)
 from ._native import last_fanout  # noqa: F401
 from .grid import ProblemSet  # noqa: F401
 
 __all__ = ["PeakSegFPOP_file", "PeakSegFPOP_dir", "PeakSegFPOP_df", "PeakSegFPOP_vec",
-           "PeakSegFPOP_dense",
+           "PeakSegFPOP_dense", "PeakSegFPOP_reads", "coverage_from_reads",
            "PeakSegFPOP_dir_batch", "sequentialSearch_dir", "sequentialSearch_dir_batch",
            "parallelSearch_dir", "parallelSearch_dir_batch",
            "writeBedGraph", "col_name_list", "paste",

@@ -14,6 +14,7 @@ ERROR_NO_HIP_DEVICE = 12
 ERROR_DEVICE_SOLVER = 13
 ERROR_DEVICE_MEMORY = 14
 ERROR_DENSE_ARGUMENTS = 17
+ERROR_READS_ARGUMENTS = 18
 
 
 class PsdResult(ctypes.Structure):
@@ -192,6 +193,17 @@ def declare(lib):
     lib.peakseg_hip_segment_stats_tile_runs.restype = c.c_int
     lib.peakseg_hip_segment_stats_last_ms.argtypes = [c.POINTER(c.c_float)]
     lib.peakseg_hip_segment_stats_last_ms.restype = c.c_int
+    reads = [c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p),
+             c.POINTER(c.c_void_p), c.POINTER(c.c_void_p), c.c_int, c.POINTER(c.c_int),
+             c.POINTER(c.c_int), c.c_int]
+    lib.peakseg_hip_problem_set_create_reads.argtypes = reads + [
+        c.c_int, c.POINTER(c.c_int), c.POINTER(c.c_double), c.c_ulonglong, c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_create_reads.restype = c.c_int
+    lib.peakseg_hip_reads_pileup_probe.argtypes = reads + [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_reads_pileup_probe.restype = c.c_int
+    lib.peakseg_hip_reads_last_pileup_ms.argtypes = [c.POINTER(c.c_float), c.POINTER(c.c_float)]
+    lib.peakseg_hip_reads_last_pileup_ms.restype = c.c_int
     return lib
 
 
@@ -221,6 +233,8 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_pack_segment_stats",
     "peakseg_hip_problem_set_packed_segment_stats_download",
     "peakseg_hip_segment_stats_tile_runs", "peakseg_hip_segment_stats_last_ms",
+    "peakseg_hip_problem_set_create_reads", "peakseg_hip_reads_pileup_probe",
+    "peakseg_hip_reads_last_pileup_ms",
 ]
 
 if not os.path.exists(LIB_PATH):

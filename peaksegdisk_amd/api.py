@@ -316,69 +316,56 @@ def _read_text_table(text, names):
                        float_precision="round_trip")
 
 
-def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=None, device=0,
-                      stats=False):
-    """PeakSegFPOP_vec without its files: dense integer coverage (one count per base) is
-    run-length encoded and solved on the GPU, and the reference's result comes back as data
-    frames.  count_vecs: one vector or a list of them (int32 numpy arrays or torch tensors are
-    passed as they are -- a tensor on cuda:`device` is never copied --, other integer arrays
-    are converted); penalties: one list for all vectors or one list per vector; chrom_starts:
-    the coordinate of each vector's first base (default 0).  Returns, for a single vector, a
-    list over its penalties, else a list over vectors of such lists, of PeakSegFPOP_dir_result
-    whose $segments and $loss are what PeakSegFPOP_dir reads from the files the file path
-    writes for the same runs (means pass through the files' "%g", penalties through paste()).
-    stats=True: every result also gets .stats, a data frame with one row per row of .segments and
-    the columns reads (the sum of the segment's bases' counts), max.count, summitStart and
-    summitEnd (the first run of the segment whose count is max.count), computed on the GPU from
-    the resident runs (ProblemSet.segment_stats)."""
-    from .grid import ProblemSet
-    single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
-        len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
-    vecs = [count_vecs] if single else list(count_vecs)
-    if len(vecs) == 0:
-        raise ValueError("count.vecs must hold at least one vector")
+def _int32_vector(v, name="count.vec"):
+    """an integer vector as the library takes it: int32 arrays and tensors as they are, other
+    integer arrays converted when they fit"""
+    if hasattr(v, "data_ptr"):
+        return v
+    v = np.asarray(v)
+    if not np.issubdtype(v.dtype, np.integer):
+        raise ValueError("%s must be integer" % name)
+    if v.dtype != np.int32:
+        if v.size and (v.max() > 2 ** 31 - 1 or v.min() < -2 ** 31):
+            raise ValueError("%s must fit 32-bit integers" % name)
+        v = v.astype(np.int32)
+    return np.ascontiguousarray(v)
+
+
+def _penalty_lists(penalties, n_contigs, noun):
+    """one list of penalties for all contigs, or one per contig -> one per contig, checked"""
     pens = list(penalties) if not isinstance(penalties, (int, float, np.integer, np.floating)) \
         else [penalties]
     per_vec = len(pens) > 0 and isinstance(pens[0], (list, tuple, np.ndarray))
     if per_vec:
-        if len(pens) != len(vecs):
-            raise ValueError("penalties: one list per vector (%d lists, %d vectors)"
-                             % (len(pens), len(vecs)))
+        if len(pens) != n_contigs:
+            raise ValueError("penalties: one list per %s (%d lists, %d %ss)"
+                             % (noun, len(pens), n_contigs, noun))
         pens = [list(q) for q in pens]
     else:
-        pens = [pens] * len(vecs)
+        pens = [pens] * n_contigs
     for q in pens:
         for pen_num in q:
             _check_pen_num(pen_num)
-    contigs = []
-    for v in vecs:
-        if not hasattr(v, "data_ptr"):
-            v = np.asarray(v)
-            if not np.issubdtype(v.dtype, np.integer):
-                raise ValueError("count.vec must be integer")
-            if v.dtype != np.int32:
-                if v.size and (v.max() > 2 ** 31 - 1 or v.min() < -2 ** 31):
-                    raise ValueError("count.vec must fit 32-bit integers")
-                v = v.astype(np.int32)
-            v = np.ascontiguousarray(v)
-        contigs.append(v)
-    if chrom_starts is None:
-        chrom_starts = [0] * len(vecs)
-    if len(chrom_starts) != len(vecs):
-        raise ValueError("chrom.starts: one per vector")
+    return pens
+
+
+def _solve_dense_set(make_set, pens, chrom, stats, single, label):
+    """What PeakSegFPOP_dense and PeakSegFPOP_reads share: the problems of `pens` (one list per
+    contig), the set -- make_set(problems) -> (ProblemSet, chromStart of each contig's first
+    base) --, its solution, and the reference's data frames, nested as `pens` is."""
     problems, pen_strs = [], []
     for c, q in enumerate(pens):
         for pen_num in q:
             pen_strs.append(paste(pen_num))
             problems.append((c, float(pen_strs[-1])))
     if not problems:
-        return [] if single else [[] for _ in vecs]
+        return [] if single else [[] for _ in pens]
     t0 = time.time()
     try:
-        pset = ProblemSet.from_dense(contigs, problems, device=device)
+        pset, chrom_starts = make_set(problems)
     except RuntimeError as e:
         status = getattr(e, "status", _native.ERROR_DEVICE_SOLVER)
-        msg = _native.status_message(status, "<dense counts>", "", "")
+        msg = _native.status_message(status, label, "", "")
         detail = _native.last_error()
         raise PeakSegError(status, "%s (%s)" % (msg, detail) if detail else msg)
     try:
@@ -421,6 +408,108 @@ def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=No
         out.append(flat[o:o + len(q)])
         o += len(q)
     return out[0] if single else out
+
+
+def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=None, device=0,
+                      stats=False):
+    """PeakSegFPOP_vec without its files: dense integer coverage (one count per base) is
+    run-length encoded and solved on the GPU, and the reference's result comes back as data
+    frames.  count_vecs: one vector or a list of them (int32 numpy arrays or torch tensors are
+    passed as they are -- a tensor on cuda:`device` is never copied --, other integer arrays
+    are converted); penalties: one list for all vectors or one list per vector; chrom_starts:
+    the coordinate of each vector's first base (default 0).  Returns, for a single vector, a
+    list over its penalties, else a list over vectors of such lists, of PeakSegFPOP_dir_result
+    whose $segments and $loss are what PeakSegFPOP_dir reads from the files the file path
+    writes for the same runs (means pass through the files' "%g", penalties through paste()).
+    stats=True: every result also gets .stats, a data frame with one row per row of .segments and
+    the columns reads (the sum of the segment's bases' counts), max.count, summitStart and
+    summitEnd (the first run of the segment whose count is max.count), computed on the GPU from
+    the resident runs (ProblemSet.segment_stats)."""
+    from .grid import ProblemSet
+    single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
+        len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
+    vecs = [count_vecs] if single else list(count_vecs)
+    if len(vecs) == 0:
+        raise ValueError("count.vecs must hold at least one vector")
+    pens = _penalty_lists(penalties, len(vecs), "vector")
+    contigs = [_int32_vector(v) for v in vecs]
+    if chrom_starts is None:
+        chrom_starts = [0] * len(vecs)
+    if len(chrom_starts) != len(vecs):
+        raise ValueError("chrom.starts: one per vector")
+    return _solve_dense_set(
+        lambda problems: (ProblemSet.from_dense(contigs, problems, device=device), chrom_starts),
+        pens, chrom, stats, single, "<dense counts>")
+
+
+# ---- aligned reads in memory (additive: the pile-up happens on the GPU) -----------------------
+
+def _read_contigs(reads):
+    """(is it a single contig, the list of contigs) of PeakSegFPOP_reads' first argument"""
+    if len(reads) == 0:
+        raise ValueError("reads must hold at least one contig")
+    first = reads[0]
+    single = not isinstance(first, (tuple, list)) or (
+        len(first) > 0 and isinstance(first[0], (int, np.integer)))
+    return single, [reads] if single else list(reads)
+
+
+def PeakSegFPOP_reads(reads, penalties, chrom="chrUnknown", extents=None, bases_counted="each",
+                      device=0, stats=False):
+    """PeakSegFPOP_dense with the step in front of it: aligned reads are piled up into coverage,
+    run-length encoded and solved on the GPU.  reads: one contig -- (chromStart, chromEnd) or
+    (chromStart, chromEnd, count), one entry per read, in any order -- or a list of contigs
+    (int32 numpy arrays or torch tensors are passed as they are, a tensor on cuda:`device` is
+    never copied; other integer arrays are converted); penalties: one list for all contigs or one
+    per contig; extents: per contig (a single pair for a single contig) the (chromStart, chromEnd)
+    whose bases are the data, default (min chromStart, max chromEnd) of its reads;
+    bases_counted: "each" base of a read or only its "end".  Coordinates are genomic: base 0 of a
+    contig is its extent's chromStart.  Results and `stats` as PeakSegFPOP_dense."""
+    from .grid import ProblemSet
+    single, contigs = _read_contigs(reads)
+    names = ("chromStart", "chromEnd", "count")
+    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
+               if isinstance(entry, (tuple, list)) else entry for entry in contigs]
+    if single and extents is not None:
+        extents = [extents]
+    pens = _penalty_lists(penalties, len(contigs), "contig")
+
+    def make_set(problems):
+        pset = ProblemSet.from_reads(contigs, problems, extents=extents,
+                                     bases_counted=bases_counted, device=device)
+        return pset, pset.contig_starts
+    return _solve_dense_set(make_set, pens, chrom, stats, single, "<aligned reads>")
+
+
+def coverage_from_reads(chromStart, chromEnd, count=None, chrom="chrUnknown", extent=None,
+                        bases_counted="each", device=0):
+    """The coverage profile of one contig's aligned reads, piled up and run-length encoded on the
+    GPU (peakseg_hip_reads_pileup_probe): the data frame chrom, chromStart, chromEnd, count that
+    writeBedGraph and PeakSegFPOP_df take -- integer columns, genomic coordinates, runs of zero
+    included, so there are no gaps.  The read arrays as ProblemSet.from_reads takes them;
+    extent: the (chromStart, chromEnd) to cover, default (min chromStart, max chromEnd)."""
+    import ctypes
+    from .grid import reads_arguments
+    entry = (chromStart, chromEnd) if count is None else (chromStart, chromEnd, count)
+    args, keep, ext = reads_arguments([entry], None if extent is None else [extent],
+                                      bases_counted, device, "coverage_from_reads")
+    lo, hi = ext[0]
+    # a read changes the coverage in at most two places
+    capacity = max(1, min(hi - lo, 2 * int(args[1][0]) + 1))
+    runs = np.zeros(1, dtype=np.int64)
+    cols = [np.empty(capacity, dtype=np.int32) for _ in range(3)]
+    st = _native.lib.peakseg_hip_reads_pileup_probe(
+        device, *args, None, runs.ctypes.data, *[a.ctypes.data for a in cols])
+    del keep
+    if st != 0:
+        msg = _native.status_message(st, "<aligned reads>", "", "")
+        detail = _native.last_error()
+        raise PeakSegError(st, "%s (%s)" % (msg, detail) if detail else msg)
+    k = int(runs[0])
+    value, weight, end = (a[:k] for a in cols)
+    return pd.DataFrame({"chrom": chrom, "chromStart": (lo + end - weight).astype(np.int32),
+                         "chromEnd": (lo + end).astype(np.int32), "count": value.copy()},
+                        columns=col_name_list["coverage"])
 
 
 # ---- PeakSegFPOP_dir for a batch (additive; SURVEY.md section 8 f3) --------------------------

@@ -1,5 +1,6 @@
 /* peakseg_dense.h -- the host side of dense coverage: the run-length encoding on the device
- * (kernels: dense_encode.h), the creator from dense counts, the loss row of a solved problem. */
+ * (kernels: dense_encode.h), the creator from dense counts and what it shares with the creator from
+ * reads (peakseg_reads.h), the loss row of a solved problem. */
 
 namespace {
 
@@ -193,6 +194,23 @@ int dense_encode(int n_contigs, const long long *n_bases, const int *const *coun
   return 0;
 }
 
+/* the probes' end: the encoded arrays to the host (any may be NULL), then freed */
+int dense_download_and_free(DenseEncoded &enc, int *count_out, int *weight_out, int *run_end_out) {
+  const size_t bytes = sizeof(int) * (size_t)enc.total_runs;
+  hipError_t e = hipSuccess;
+  if (count_out) e = hipMemcpy(count_out, enc.count, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && weight_out) e = hipMemcpy(weight_out, enc.weight, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && run_end_out) e = hipMemcpy(run_end_out, enc.run_end, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(enc.count);
+  (void)hipFree(enc.weight);
+  (void)hipFree(enc.run_end);
+  if (e != hipSuccess) {
+    set_error("dense counts: download failed: %s", hipGetErrorString(e));
+    return ERROR_DEVICE_SOLVER;
+  }
+  return 0;
+}
+
 thread_local float g_dense_ms[3] = {0.f, 0.f, 0.f};
 
 }  // namespace
@@ -228,31 +246,13 @@ extern "C" int peakseg_hip_dense_encode_probe(int device, int n_contigs, const l
     if (max_out) max_out[c] = enc.stats[(size_t)c].mx;
     if (sum_out) sum_out[c] = enc.stats[(size_t)c].sum;
   }
-  const size_t bytes = sizeof(int) * (size_t)enc.total_runs;
-  hipError_t e = hipSuccess;
-  if (count_out) e = hipMemcpy(count_out, enc.count, bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && weight_out) e = hipMemcpy(weight_out, enc.weight, bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && run_end_out) e = hipMemcpy(run_end_out, enc.run_end, bytes, hipMemcpyDeviceToHost);
-  (void)hipFree(enc.count);
-  (void)hipFree(enc.weight);
-  (void)hipFree(enc.run_end);
-  if (e != hipSuccess) {
-    set_error("dense counts: download failed: %s", hipGetErrorString(e));
-    return ERROR_DEVICE_SOLVER;
-  }
-  return 0;
+  return dense_download_and_free(enc, count_out, weight_out, run_end_out);
 }
 
-extern "C" int peakseg_hip_problem_set_create_dense(int device, int n_contigs,
-                                                    const long long *contig_n_bases,
-                                                    const int *const *contig_counts,
-                                                    int counts_on_device, int n_problems,
-                                                    const int *problem_contig,
-                                                    const double *problem_penalty,
-                                                    unsigned long long arena_pieces,
-                                                    psd_problem_set **out) {
-  *out = nullptr;
-  /* penalties first: the reference validates them before it opens its input (drv:145-159) */
+namespace {
+
+/* penalties first: the reference validates them before it opens its input (drv:145-159) */
+int dense_check_penalties(int n_problems, const double *problem_penalty) {
   for (int p = 0; p < n_problems; p++) {
     const double pen = problem_penalty[p];
     if (pen == INFINITY) continue;
@@ -265,8 +265,11 @@ extern "C" int peakseg_hip_problem_set_create_dense(int device, int n_contigs,
       return ERROR_PENALTY_NEGATIVE;
     }
   }
-  int st = dense_check_lengths(n_contigs, contig_n_bases);
-  if (st) return st;
+  return 0;
+}
+
+/* the device and the problem list, once the host has nothing left to say about the data */
+int dense_check_device_problems(int device, int n_contigs, int n_problems, const int *problem_contig) {
   if (peakseg_hip_device_count() <= device || device < 0) {
     set_error("no HIP device %d visible (this library has no CPU fallback)", device);
     return ERROR_NO_HIP_DEVICE;
@@ -280,11 +283,17 @@ extern "C" int peakseg_hip_problem_set_create_dense(int device, int n_contigs,
       set_error("problem %d names contig %d", p, problem_contig[p]);
       return ERROR_DEVICE_SOLVER;
     }
-  HIP_TRY(hipSetDevice(device));
-  CreateLaps lap;
-  DenseEncoded enc;
-  st = dense_encode(n_contigs, contig_n_bases, contig_counts, counts_on_device, enc);
-  if (st) return st;
+  return 0;
+}
+
+/* What every creator of a dense set does once dense_encode() has succeeded: the encoder's laps,
+ * the set around the encoded arrays (which it owns from here on), create_common.  `lap` has been
+ * running since the creator began. */
+int dense_create_encoded(int device, int n_contigs, const long long *contig_n_bases,
+                         int counts_on_device, DenseEncoded &enc, CreateLaps &lap, int n_problems,
+                         const int *problem_contig, const double *problem_penalty,
+                         unsigned long long arena_pieces, psd_problem_set **out) {
+  int st = 0;
   for (int k = 0; k < 3; k++) g_dense_ms[k] = enc.ms[k];
   if (lap.on) {
     fprintf(stderr, "peakseg_hip timing: create: %-26s %8.3f s\n",
@@ -321,6 +330,29 @@ extern "C" int peakseg_hip_problem_set_create_dense(int device, int n_contigs,
   if ((st = dev_alloc(s, &s->d_order_run, (size_t)n_problems))) return st;
   return create_common(std::move(set), lap, min_lm, max_lm, nullptr, nullptr, problem_contig, problem_penalty,
                        arena_pieces, out);
+}
+
+}  // namespace
+
+extern "C" int peakseg_hip_problem_set_create_dense(int device, int n_contigs,
+                                                    const long long *contig_n_bases,
+                                                    const int *const *contig_counts,
+                                                    int counts_on_device, int n_problems,
+                                                    const int *problem_contig,
+                                                    const double *problem_penalty,
+                                                    unsigned long long arena_pieces,
+                                                    psd_problem_set **out) {
+  *out = nullptr;
+  int st = dense_check_penalties(n_problems, problem_penalty);
+  if (st) return st;
+  if ((st = dense_check_lengths(n_contigs, contig_n_bases))) return st;
+  if ((st = dense_check_device_problems(device, n_contigs, n_problems, problem_contig))) return st;
+  HIP_TRY(hipSetDevice(device));
+  CreateLaps lap;
+  DenseEncoded enc;
+  if ((st = dense_encode(n_contigs, contig_n_bases, contig_counts, counts_on_device, enc))) return st;
+  return dense_create_encoded(device, n_contigs, contig_n_bases, counts_on_device, enc, lap, n_problems,
+                              problem_contig, problem_penalty, arena_pieces, out);
 }
 
 /* the reference's loss row: write_dp_outputs and write_trivial in peakseg_files.h */

@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -80,6 +80,8 @@
 #include "dense_encode.h"
 /* reads, maximum and summit of every segment from the resident runs */
 #include "segment_stats.h"
+/* coverage from aligned reads: the pile-up the dense encoder reads in place */
+#include "reads_pileup.h"
 
 #include <ctype.h>
 #include <errno.h>
@@ -114,6 +116,7 @@
 #include "peakseg_solve.h"
 #include "peakseg_pack.h"
 #include "peakseg_dense.h"
+#include "peakseg_reads.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -465,6 +468,10 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
     PSD_MESSAGE(ERROR_DENSE_ARGUMENTS,
                 "error code %d: dense counts that cannot be solved (2^31 or more bases, a negative "
                 "count, counts that sum to 2^53 or more, or 2^30 or more runs in a contig)", status);
+    PSD_MESSAGE(ERROR_READS_ARGUMENTS,
+                "error code %d: aligned reads that cannot be piled up (an empty or negative extent, a "
+                "read with chromStart >= chromEnd or a negative count, or counts that sum to 2^31 or "
+                "more in a contig)", status);
     default:
       snprintf(buf, buf_len, "error code %d", status);
       break;

@@ -169,9 +169,10 @@ PSD_D void agent_store_ptr(char **p, char *v) {
 }
 #endif
 
-/* 64-bit integer atomics on words in HBM that other workgroups of the launch update too; nothing
- * is returned, so the device issues them and goes on */
+/* integer atomics on words in HBM that other workgroups of the launch update too; nothing is
+ * returned, so the device issues them and goes on */
 #ifdef PSD_EMU
+PSD_D void atomic_add_i32(int *p, int v) { (void)__atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 PSD_D void atomic_add_i64(long long *p, long long v) { (void)__atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 PSD_D void atomic_max_u64(unsigned long long *p, unsigned long long v) {
   unsigned long long o = __atomic_load_n(p, __ATOMIC_RELAXED);
@@ -179,6 +180,9 @@ PSD_D void atomic_max_u64(unsigned long long *p, unsigned long long v) {
   }
 }
 #else
+PSD_D void atomic_add_i32(int *p, int v) {
+  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 PSD_D void atomic_add_i64(long long *p, long long v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

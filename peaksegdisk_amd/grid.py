@@ -8,32 +8,101 @@ import numpy as np
 from . import _native
 
 
-def _dense_pointer(k, v, device):
+def _dense_pointer(k, v, device, what="from_dense: contig %d"):
     """(address, length, "host" | "device", the object that keeps the memory alive) of contig k
-    of ProblemSet.from_dense; ValueError for what cannot be passed as it is."""
+    of ProblemSet.from_dense (`what`: how the messages name it; from_reads names the array too);
+    ValueError for what cannot be passed as it is."""
+    what = what % k
     if isinstance(v, np.ndarray):
         if v.dtype != np.int32:
-            raise ValueError("from_dense: contig %d has dtype %s, not int32" % (k, v.dtype))
+            raise ValueError("%s has dtype %s, not int32" % (what, v.dtype))
         if v.ndim != 1 or not v.flags["C_CONTIGUOUS"]:
-            raise ValueError("from_dense: contig %d is not a contiguous 1-d array" % k)
+            raise ValueError("%s is not a contiguous 1-d array" % what)
         return v.ctypes.data, v.shape[0], "host", v
     if type(v).__module__.split(".")[0] == "torch" and hasattr(v, "data_ptr"):
         import torch
         if v.dtype != torch.int32:
-            raise ValueError("from_dense: contig %d has dtype %s, not int32" % (k, v.dtype))
+            raise ValueError("%s has dtype %s, not int32" % (what, v.dtype))
         if v.dim() != 1 or not v.is_contiguous():
-            raise ValueError("from_dense: contig %d is not a contiguous 1-d tensor" % k)
+            raise ValueError("%s is not a contiguous 1-d tensor" % what)
         if v.device.type == "cuda":
             index = v.device.index if v.device.index is not None else torch.cuda.current_device()
             if index != device:
-                raise ValueError("from_dense: contig %d is on cuda:%d, the set on device %d"
-                                 % (k, index, device))
+                raise ValueError("%s is on cuda:%d, the set on device %d"
+                                 % (what, index, device))
             return v.data_ptr(), v.shape[0], "device", v
         if v.device.type != "cpu":
-            raise ValueError("from_dense: contig %d is on device %s" % (k, v.device))
+            raise ValueError("%s is on device %s" % (what, v.device))
         return v.data_ptr(), v.shape[0], "host", v
-    raise ValueError("from_dense: contig %d is a %s, not an int32 numpy array or torch tensor"
-                     % (k, type(v).__name__))
+    raise ValueError("%s is a %s, not an int32 numpy array or torch tensor"
+                     % (what, type(v).__name__))
+
+
+def _extreme(v, largest):
+    """the smallest or largest entry of a read array, wherever it lives"""
+    return int((v.max() if largest else v.min()).item())
+
+
+def reads_arguments(reads, extents, bases_counted, device, who):
+    """The read arguments of the C ABI (peakseg_hip_problem_set_create_reads and
+    peakseg_hip_reads_pileup_probe) from `reads`: a list, one entry per contig, of
+    (chromStart, chromEnd) or (chromStart, chromEnd, count) int32 arrays, validated as from_dense
+    validates its contigs.  Returns (the nine ctypes arguments after `device`, the objects
+    that keep the memory alive, the extents as a list of (lo, hi))."""
+    if len(reads) == 0:
+        raise ValueError("%s: no contig" % who)
+    if isinstance(bases_counted, str):
+        if bases_counted not in ("each", "end"):
+            raise ValueError('%s: bases_counted is %r, neither "each" nor "end"' % (who, bases_counted))
+        mode = 0 if bases_counted == "each" else 1
+    else:
+        mode = int(bases_counted)
+    if extents is not None and len(extents) != len(reads):
+        raise ValueError("%s: extents: one (chromStart, chromEnd) per contig" % who)
+    names = ("chromStart", "chromEnd", "count")
+    keep, sides, lengths, out_extents = [], [], [], []
+    ptrs = ([], [], [])
+    for k, entry in enumerate(reads):
+        if not isinstance(entry, (tuple, list)) or len(entry) not in (2, 3):
+            raise ValueError("%s: contig %d is not (chromStart, chromEnd) or "
+                             "(chromStart, chromEnd, count)" % (who, k))
+        n = None
+        for j in range(3):
+            v = entry[j] if j < len(entry) else None
+            if v is None:
+                if j < 2:
+                    raise ValueError("%s: contig %d has no %s" % (who, k, names[j]))
+                ptrs[j].append(0)
+                continue
+            ptr, m, side, ref = _dense_pointer(k, v, device, who + ": contig %d " + names[j])
+            if n is not None and m != n:
+                raise ValueError("%s: contig %d has %d chromStart and %d %s"
+                                 % (who, k, n, m, names[j]))
+            n = m
+            keep.append(ref)
+            sides.append((side, k))
+            ptrs[j].append(ptr if m else 0)
+        lengths.append(n)
+        if extents is None:
+            if n == 0:
+                raise ValueError("%s: contig %d has no reads: its extent must be given" % (who, k))
+            out_extents.append((_extreme(entry[0], False), _extreme(entry[1], True)))
+        else:
+            out_extents.append((int(extents[k][0]), int(extents[k][1])))
+    for side, k in sides:
+        if side != sides[0][0]:
+            raise ValueError("%s: contig %d is in %s memory but contig 0 is in %s memory; "
+                             "one call takes one kind" % (who, k, side, sides[0][0]))
+    for lo, hi in out_extents:
+        if not (-2 ** 31 <= lo < 2 ** 31 and -2 ** 31 <= hi < 2 ** 31):
+            raise ValueError("%s: extents must fit 32-bit integers" % who)
+    nc = len(reads)
+    args = [nc, (ctypes.c_longlong * nc)(*lengths)]
+    args += [(ctypes.c_void_p * nc)(*p) for p in ptrs]
+    args += [1 if sides[0][0] == "device" else 0,
+             (ctypes.c_int * nc)(*[lo for lo, _ in out_extents]),
+             (ctypes.c_int * nc)(*[hi for _, hi in out_extents]), mode]
+    return args, keep, out_extents
 
 
 class ProblemSet:
@@ -101,6 +170,43 @@ class ProblemSet:
         del keep  # (the library holds no reference to the caller's buffers after the call)
         if st != 0:
             err = RuntimeError("peakseg_hip_problem_set_create_dense: status %d: %s" % (
+                st, self._lib.peakseg_hip_last_error().decode()))
+            err.status = st
+            raise err
+        self.contigs = None
+        self.bins_per_solve = None
+        return self
+
+    @classmethod
+    def from_reads(cls, reads, problems, extents=None, bases_counted="each", device=0,
+                   arena_pieces=0, lib=None):
+        """The set of ALIGNED READS: `reads` is a list, one entry per contig, of
+        (chromStart, chromEnd) or (chromStart, chromEnd, count) -- 1-d contiguous int32 numpy
+        arrays or torch tensors, one entry per read, in any order.  The coverage is piled up and
+        run-length encoded on the device (peakseg_hip_problem_set_create_reads); tensors on
+        cuda:`device` are read in place, numpy arrays and CPU tensors are uploaded by the library;
+        one call takes one kind of memory.  extents: per contig the (chromStart, chromEnd) whose
+        bases are the contig's data, reads clipped to it; None: (min chromStart, max chromEnd) of
+        the contig's reads.  bases_counted: "each" base of a read, or only its "end" (last base).
+        From here on the set is one of from_dense: contig_bases are the extents' lengths and
+        contig_starts their starts, so segment_columns(first_chromStart=pset.contig_starts) gives
+        genomic coordinates."""
+        self = cls.__new__(cls)
+        self._lib = lib or _native.lib
+        self._h = ctypes.c_void_p()
+        self.dense = True
+        self.problems = [(int(c), float(p)) for c, p in problems]
+        args, keep, ext = reads_arguments(reads, extents, bases_counted, device, "from_reads")
+        self.contig_starts = [lo for lo, _ in ext]
+        self.contig_bases = [hi - lo for lo, hi in ext]
+        npb = len(self.problems)
+        pc = (ctypes.c_int * max(npb, 1))(*[c for c, _ in self.problems])
+        pp = (ctypes.c_double * max(npb, 1))(*[p for _, p in self.problems])
+        st = self._lib.peakseg_hip_problem_set_create_reads(
+            device, *args, npb, pc, pp, ctypes.c_ulonglong(arena_pieces), ctypes.byref(self._h))
+        del keep  # (the library holds no reference to the caller's buffers after the call)
+        if st != 0:
+            err = RuntimeError("peakseg_hip_problem_set_create_reads: status %d: %s" % (
                 st, self._lib.peakseg_hip_last_error().decode()))
             err.status = st
             raise err

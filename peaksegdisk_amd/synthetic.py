@@ -76,6 +76,30 @@ def poisson_coverage(n_bins, seed=1):
     return chrom_start.astype(np.int32), chrom_end.astype(np.int32), count.astype(np.int32)
 
 
+def poisson_reads(n_bins, seed=1):
+    """Aligned reads placed by poisson_coverage's piecewise rate: every bin of that coverage starts
+    `count` reads at positions uniform over the bin, lengths uniform on 20..115 (ChIPreads' range).
+    Returns (chromStart, chromEnd) int32 arrays sorted by chromStart and the extent (0, the
+    coverage's last chromEnd); reads that run over the extent's end are left to be clipped."""
+    cs, ce, cnt = poisson_coverage(n_bins, seed=seed)
+    n = int(cnt.sum(dtype=np.int64))
+    bin_of = np.repeat(np.arange(len(cnt)), cnt)
+    width = (ce - cs).astype(np.int64)[bin_of]
+    start = cs.astype(np.int64)[bin_of] + np.floor(uniform01(seed, 5, n) * width).astype(np.int64)
+    length = 20 + np.floor(uniform01(seed, 6, n) * 96.0).astype(np.int64)
+    order = np.argsort(start, kind="stable")
+    start, end = start[order], (start + length)[order]
+    if n and end.max() >= 2 ** 31:
+        raise ValueError("synthetic reads exceed int32 coordinates")
+    return start.astype(np.int32), end.astype(np.int32), (0, int(ce[-1]))
+
+
+def shuffled(seed, *arrays):
+    """the arrays in one seeded random order (reads as an unsorted BAM would give them)"""
+    order = np.argsort(uniform01(seed, 7, len(arrays[0])), kind="stable")
+    return tuple(a[order] for a in arrays)
+
+
 def increasing_coverage(n_bins):
     """Worst case of vignettes/Worst_case.Rmd:26-28: count = 1..N, width 1."""
     n_bins = int(n_bins)

@@ -21,8 +21,20 @@
     the launch must move (12 R per problem + 24 per row), that figure's share of the copy rate,
     and the forward kernel's time for the same set.
 
+(r) --reads: the path from aligned reads and nothing else.  Synthetic reads
+    (synthetic.poisson_reads: lengths 20-115, placed by the piecewise Poisson rate) for the extent
+    of (a) and for the contigs of (b), each once sorted by chromStart and once shuffled:
+      r_pileup  HIP events of the pile-up (zeroing + scatter; the three scan launches), warmed,
+                --reps repetitions, minimum / median / maximum
+      r_legs    three ways to a solved set, alternating in one process, results compared for
+                equality before any time is printed: from_reads on cuda tensors, from_reads on
+                numpy arrays, and numpy add.at + cumsum per contig followed by from_dense.  Each leg
+                is timed up to the finished set (creation), then solved; the forward kernel's time
+                is the solve's.  For the one-contig set the legs run on its first
+                --reads-solve-bases bases (the whole contig's solve takes minutes).
+
 usage: python tools/dense_timing.py [--contigs 6144] [--reps 20] [--e2e-reps 2] [--skip-long]
-       [--skip-e2e] [--skip-stats]
+       [--skip-e2e] [--skip-stats] [--reads [--reads-bins 10000000] [--reads-solve-bases 2500000]]
 One JSON line per part on stdout."""
 import argparse
 import ctypes
@@ -50,8 +62,15 @@ ap.add_argument("--e2e-reps", type=int, default=2)
 ap.add_argument("--skip-long", action="store_true")
 ap.add_argument("--skip-e2e", action="store_true")
 ap.add_argument("--skip-stats", action="store_true")
+ap.add_argument("--reads", action="store_true")
+ap.add_argument("--reads-bins", type=int, default=10 ** 7)
+ap.add_argument("--reads-solve-bases", type=int, default=2500000)
 args = ap.parse_args()
 lib = _native.lib
+
+
+def mmm(v):
+    return {"min": min(v), "median": statistics.median(v), "max": max(v)}
 
 
 def expand(cnt, width):
@@ -77,9 +96,6 @@ def encoder_laps(tensors, reps):
     bases = sum(len(t) for t in tensors)
     total = [sum(l) for l in laps]
     traffic = 8.0 * bases + 12.0 * float(runs.sum())
-
-    def mmm(v):
-        return {"min": min(v), "median": statistics.median(v), "max": max(v)}
     med = statistics.median(total)
     return {"contigs": nc, "bases": bases, "runs": int(runs.sum()), "reps": reps,
             "traffic_bytes": traffic,
@@ -128,6 +144,124 @@ def stats_laps(part, tensors_, problems_, reps):
            "forward_kernel_ms": forward_ms, "kernel_build": build,
            "stats_share_of_forward": med / forward_ms if forward_ms > 0 else None}
     print(json.dumps(out), flush=True)
+
+
+def pileup_laps(contigs, extents, reps):
+    """HIP events of the pile-up alone (no encoding) on device tensors"""
+    from peaksegdisk_amd.grid import reads_arguments
+    r_args, keep, _ = reads_arguments(contigs, extents, "each", 0, "dense_timing")
+    laps = []
+    torch.cuda.synchronize()
+    for k in range(reps + 3):
+        st = lib.peakseg_hip_reads_pileup_probe(0, *r_args, None, None, None, None, None)
+        assert st == 0, _native.last_error()
+        ms = [ctypes.c_float(), ctypes.c_float()]
+        lib.peakseg_hip_reads_last_pileup_ms(ctypes.byref(ms[0]), ctypes.byref(ms[1]))
+        if k >= 3:  # warmed
+            laps.append([m.value for m in ms])
+    n = sum(len(c[0]) for c in contigs)
+    bases = sum(hi - lo for lo, hi in extents)
+    return {"contigs": len(contigs), "reads": n, "bases": bases, "reps": reps,
+            "traffic_bytes_8n_plus_16B": 8.0 * n + 16.0 * bases,
+            "scatter_ms": mmm([l[0] for l in laps]), "scan_ms": mmm([l[1] for l in laps]),
+            "total_ms": mmm([sum(l) for l in laps])}
+
+
+def numpy_pileup(start, end, lo, hi):
+    """what a user does today: add.at on a difference array, cumsum (reads clipped to [lo, hi))"""
+    s = start.astype(np.int64)
+    e = end.astype(np.int64)
+    inside = (e > lo) & (s < hi)
+    diff = np.zeros(hi - lo + 1, np.int32)
+    np.add.at(diff, np.maximum(s[inside], lo) - lo, 1)
+    np.add.at(diff, np.minimum(e[inside], hi) - lo, -1)
+    return np.cumsum(diff[:-1], dtype=np.int32)
+
+
+def reads_legs(part, host, extents, problems_, reps):
+    """one JSON line: the three legs on the reads `host` (numpy), creation timed, then solved"""
+    device = [tuple(torch.from_numpy(v).to("cuda:0") for v in c) for c in host]
+
+    def solved(make):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        s = make()
+        t_create = time.time() - t0
+        try:
+            k_ms = s.solve()[0]
+            return t_create, k_ms, s.kernel_build, s.segment_columns(), \
+                [s.loss(p) for p in range(len(problems_))]
+        finally:
+            s.close()
+
+    legs = [("from_reads_cuda", lambda: ProblemSet.from_reads(device, problems_, extents=extents)),
+            ("from_reads_numpy", lambda: ProblemSet.from_reads(host, problems_, extents=extents)),
+            ("numpy_pileup_from_dense", lambda: ProblemSet.from_dense(
+                [numpy_pileup(c[0], c[1], lo, hi) for c, (lo, hi) in zip(host, extents)], problems_))]
+    times = {name: [] for name, _ in legs}
+    last = {}
+    for rep in range(reps + 1):  # (the first round warms every leg and is not counted)
+        for name, make in legs:
+            last[name] = solved(make)
+            if rep > 0:
+                times[name].append(last[name][0])
+    ref = last["numpy_pileup_from_dense"]
+    for name in ("from_reads_cuda", "from_reads_numpy"):
+        for p in range(len(problems_)):
+            assert all(np.array_equal(x, y) for x, y in zip(last[name][3][p], ref[3][p])), (name, p)
+            assert np.array_equal(last[name][4][p], ref[4][p]), (name, p)
+    laps = pileup_laps(device, extents, args.reps)
+    forward_ms = last["from_reads_cuda"][1]
+    out = {"part": part, "legs_equal": True, "problems": len(problems_),
+           "data_points": int(sum(ref[4][p][4] for p in range(len(problems_)))),
+           "forward_kernel_ms": forward_ms, "kernel_build": last["from_reads_cuda"][2],
+           "pileup": laps,
+           "pileup_share_of_forward": laps["total_ms"]["median"] / forward_ms if forward_ms else None}
+    for name, _ in legs:
+        out[name + "_create_s"] = mmm(times[name])
+    out["numpy_leg_over_from_reads_cuda"] = statistics.median(times["numpy_pileup_from_dense"]) / \
+        statistics.median(times["from_reads_cuda"])
+    print(json.dumps(out), flush=True)
+
+
+def reads_mode():
+    grid_ = synthetic.penalty_grid()
+    # the extent of (a)
+    if not args.skip_long:
+        s, e, ext = synthetic.poisson_reads(args.reads_bins, seed=1)
+        for order, (rs, re_) in (("sorted", (s, e)), ("shuffled", synthetic.shuffled(1, s, e))):
+            dev = [(torch.from_numpy(rs).to("cuda:0"), torch.from_numpy(re_).to("cuda:0"))]
+            print(json.dumps(dict(part="r_pileup_one_contig_" + order,
+                                  **pileup_laps(dev, [ext], args.reps))), flush=True)
+            del dev
+            if not args.skip_e2e:
+                head = (0, min(args.reads_solve_bases, ext[1]))
+                keep = rs < head[1]
+                reads_legs("r_legs_one_contig_first_bases_" + order, [(rs[keep], re_[keep])], [head],
+                           [(0, 1550.5)], args.e2e_reps)
+        torch.cuda.empty_cache()
+    # the contigs of (b)
+    sets = {"sorted": [], "shuffled": []}
+    extents = []
+    for k in range(args.contigs):
+        s, e, ext = synthetic.poisson_reads(10000, seed=k)
+        sets["sorted"].append((s, e))
+        sets["shuffled"].append(synthetic.shuffled(k, s, e))
+        extents.append(ext)
+    problems_ = [(k, float(grid_[k % 64])) for k in range(args.contigs)]
+    for order in ("sorted", "shuffled"):
+        if args.skip_e2e:
+            dev = [tuple(torch.from_numpy(v).to("cuda:0") for v in c) for c in sets[order]]
+            print(json.dumps(dict(part="r_pileup_many_contigs_" + order,
+                                  **pileup_laps(dev, extents, args.reps))), flush=True)
+            del dev
+        else:
+            reads_legs("r_legs_many_contigs_" + order, sets[order], extents, problems_, args.e2e_reps)
+
+
+if args.reads:
+    reads_mode()
+    sys.exit(0)
 
 
 if not args.skip_long:
