@@ -1,9 +1,10 @@
-/* fpop_envelope.h -- the min-envelope of two functions with their lists in LDS (or, by one
- * wave, in HBM).
+/* fpop_envelope.h -- the min-envelope of two functions.
  *
- * The candidates of a merged interval, the interval table, the classification by lanes,
- * compaction, the sequential replay (min_env_serial) and min_env_impl (fpop_wave.h describes
- * the design).
+ * Its parts, each once for every envelope: the candidates of a merged interval, the interval
+ * table, a lane's load of its interval (EnvLane), the classification by lanes, the compaction of
+ * a chunk (env_compact_chunk) and the sequential replay (min_env_serial).  min_env_impl is the
+ * envelope by one wave, lists in LDS or HBM; fpop_coop.h has the one by two waves on lists in
+ * HBM (fpop_wave.h describes the design).
  *
  * Reached only through fpop_wave.h: no include guard, compiled once per build variant into
  * namespace psd::PSD_VARIANT. */
@@ -213,6 +214,84 @@ PSD_D int rank_mx(const L &f, int n, double x) {
     }
   }
   return lo;
+}
+/* number of entries of the sorted array a[0..n) below x */
+PSD_D int rank_staged(const ldouble *a, int n, double x) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    int mid = (lo + hi) >> 1;
+    if (a[mid] < x) {
+      lo = mid + 1;
+    } else {
+      hi = mid;
+    }
+  }
+  return lo;
+}
+
+/* Merged-interval table of functions too long for the 32+32 table of min_env_impl: interval k
+ * ends at the k-th distinct max_log_mean.  First the entries owned by f1 (every end of f1);
+ * returns how many ends of f1 are also ends of f2.  staged: the ends of f2 in LDS (fpop_coop.h),
+ * or nullptr to rank in the list itself */
+template <class L, class S>
+PSD_D int env_table_first(const L &f1, int n1, const L &f2, int n2, const S &s,
+                          const ldouble *staged) {
+  const int lane = lane_id();
+  const int iv_cap = s.iv_cap();
+  int dup_before = 0; /* ends of f1 that are also ends of f2, among earlier chunks */
+  for (int base = 0; base < n1; base += WAVE) {
+    int i = base + lane;
+    bool valid = i < n1;
+    int p = 0;
+    bool dup = false;
+    if (valid) {
+      double x = f1.mx(i);
+      if (staged) {
+        p = rank_staged(staged, n2, x);
+        dup = p < n2 && staged[p] == x;
+      } else {
+        p = rank_mx(f2, n2, x);
+        dup = p < n2 && f2.mx(p) == x;
+      }
+    }
+    unsigned long long md = ballot(dup);
+    if (valid) {
+      int k = i + p - (dup_before + popc64(md & lanes_below(lane)));
+      if (k < iv_cap) s.iv(k) = (i << 16) | p;
+    }
+    dup_before += popc64(md);
+  }
+  return dup_before;
+}
+/* ... and the entries owned by f2 (its ends that are not ends of f1); staged: the ends of f1 */
+template <class L, class S>
+PSD_D void env_table_second(const L &f1, int n1, const L &f2, int n2, const S &s,
+                            const ldouble *staged) {
+  const int lane = lane_id();
+  const int iv_cap = s.iv_cap();
+  int dup_before = 0;
+  for (int base = 0; base < n2; base += WAVE) {
+    int j = base + lane;
+    bool valid = j < n2;
+    int q = 0;
+    bool dup = false;
+    if (valid) {
+      double x = f2.mx(j);
+      if (staged) {
+        q = rank_staged(staged, n1, x);
+        dup = q < n1 && staged[q] == x;
+      } else {
+        q = rank_mx(f1, n1, x);
+        dup = q < n1 && f1.mx(q) == x;
+      }
+    }
+    unsigned long long md = ballot(dup);
+    if (valid && !dup) {
+      int k = j + q - (dup_before + popc64(md & lanes_below(lane)));
+      if (k < iv_cap) s.iv(k) = (q << 16) | j;
+    }
+    dup_before += popc64(md);
+  }
 }
 
 /* Everything push_min_pieces needs for merged interval (i1,i2): loads the two pieces and
@@ -570,6 +649,120 @@ PSD_D bool bit_identical(const Coef &last, double last_prv, int last_di, const C
          (last_di == di);
 }
 
+/* What one lane holds of its merged interval: the two pieces, the interval, the candidates */
+struct EnvLane {
+  Cands cd;
+  double ia, ib;
+  Coef c1, c2;
+  double prv1, prv2;
+  int di1, di2, i1, i2;
+  int err;
+};
+template <class L, class S>
+PSD_D void env_lane_load(const L &f1, int n1, const L &f2, int n2, const S &s, int k, bool valid,
+                         EnvLane &e) {
+  e.cd.n = 0;
+  e.cd.first = 0;
+  e.cd.x1 = e.cd.x2 = 0.0;
+  e.ia = e.ib = 0.0;
+  e.c1.Linear = e.c1.Log = e.c1.Constant = 0.0;
+  e.c2 = e.c1;
+  e.prv1 = e.prv2 = 0.0;
+  e.di1 = e.di2 = e.i1 = e.i2 = 0;
+  e.err = 0;
+  if (valid) {
+    int en = s.iv(k);
+    e.i1 = en >> 16;
+    e.i2 = en & 0xffff;
+    env_load_interval(f1, n1, f2, n2, e.i1, e.i2, e.c1, e.c2, e.ia, e.ib, e.err);
+    e.prv1 = f1.prv(e.i1);
+    e.di1 = f1.di(e.i1);
+    e.prv2 = f2.prv(e.i2);
+    e.di2 = f2.di(e.i2);
+  }
+}
+/* push_piece over one chunk of 64 merged intervals, one lane per interval, by ballots and prefix
+ * scans: lane `lane` holds interval k's candidates in `e` (valid: k < K).  n_out, the number of
+ * pieces in `out`, and last_id, the source piece of the last candidate emitted so far as
+ * (list << 20) | index (-1: none), carry from chunk to chunk.  Returns 0, or -(WERR_* bits) and
+ * then nothing usable is in `out`; -WERR_SERIAL: the caller replays the intervals sequentially
+ * (min_env_serial). */
+template <class L>
+PSD_D int env_compact_chunk(const L &f1, const L &f2, const L &out, int cap, bool valid,
+                            const EnvLane &e, int &n_out, int &last_id) {
+  const int lane = lane_id();
+  const Cands &cd = e.cd;
+  /* first / last candidate of this lane */
+  const int src0 = cd.first, src1 = cd.first ^ 1; /* the third piece has source src0 again */
+  Coef fc = src0 ? e.c2 : e.c1;
+  double fprv = src0 ? e.prv2 : e.prv1;
+  int fdi = src0 ? e.di2 : e.di1;
+  int lsrc = cd.n == 2 ? src1 : src0;
+  /* piece q of this interval spans [lo_q, hi_q] */
+  const double hi0 = cd.n == 1 ? e.ib : cd.x1;
+  const double hi1 = cd.n == 2 ? e.ib : cd.x2;
+  bool has = valid && cd.n > 0;
+  unsigned long long m_has = ballot(has);
+  unsigned long long m_err = ballot(e.err != 0);
+  if (m_err) {
+    int eb = 0;
+    for (int l = 0; l < WAVE; l++) eb |= shfl_i(e.err, l);
+    return -eb;
+  }
+  /* predecessor = last candidate of the nearest lower lane that has one, else the carry.
+   * Only its identity crosses lanes; its fields are re-read from the input list. */
+  unsigned long long lb = lanes_below(lane);
+  unsigned long long below = m_has & lb;
+  const int my_last_id = (lsrc << 20) | (lsrc ? e.i2 : e.i1);
+  int pid = shfl_i(my_last_id, below ? msb64(below) : 0); /* per-lane source */
+  if (!below) pid = last_id;
+  const bool have_pred = pid >= 0;
+  /* (every lane reads a predecessor -- piece 0 where it has none -- and the tests are masked
+   * afterwards: one LDS round trip, no exec-masked region) */
+  const L &pl = (have_pred && (pid >> 20)) ? f2 : f1;
+  const int pi = have_pred ? (pid & 0xfffff) : 0;
+  const Coef pc = load_coef(pl, pi);
+  const double pprv = pl.prv(pi);
+  const int pdi = pl.di(pi);
+  const bool follows = has & have_pred;
+  const bool co = follows & coalesces(pc, pprv, pdi, fc, fprv, fdi);
+  const bool bi = bit_identical(pc, pprv, pdi, fc, fprv, fdi);
+  const bool head0 = !co; /* does the first candidate start a new output piece? */
+  const bool fuzzy = co & !bi;
+  /* candidates 2 and 3 of a lane alternate it1/it2 with same_funs(it1,it2) false, so
+   * they always start a new piece -- provided the run they follow is bit-identical to
+   * its head, which `fuzzy` checks. */
+  if (ballot(fuzzy)) return -WERR_SERIAL;
+  int heads = has ? ((head0 ? 1 : 0) + (cd.n - 1)) : 0;
+  unsigned long long hb0 = ballot((heads & 1) != 0);
+  unsigned long long hb1 = ballot((heads & 2) != 0);
+  int heads_before = popc64(hb0 & lb) + 2 * popc64(hb1 & lb);
+  int heads_total = popc64(hb0) + 2 * popc64(hb1);
+  if (n_out + heads_total > cap) return -WERR_OVERFLOW;
+  int slot = n_out + heads_before - (head0 ? 0 : 1); /* piece candidate 0 belongs to */
+  if (has & head0) store_piece(out, slot, fc, e.ia, hi0, fdi, fprv);
+  if (has & (cd.n >= 2)) {
+    Coef c = src1 ? e.c2 : e.c1;
+    store_piece(out, slot + 1, c, cd.x1, hi1, src1 ? e.di2 : e.di1, src1 ? e.prv2 : e.prv1);
+  }
+  if (has & (cd.n >= 3)) store_piece(out, slot + 2, fc, cd.x2, e.ib, fdi, fprv);
+  wave_sync();
+  /* a candidate that extends the previous piece only moves that piece's right end; of
+   * the members of a run only the last one (in this chunk) writes, after the heads. */
+  {
+    const unsigned long long m_head0 = ballot(has & head0);
+    const unsigned long long above = m_has & ~lb & ~(1ull << lane);
+    /* (bit 63 keeps ctz64 defined for the top lane of the run; it never is the lowest bit
+     * of a non-empty `above`) */
+    const bool next_is_head = !above | (((m_head0 >> ctz64(above | (1ull << 63))) & 1ull) != 0);
+    if (has & !head0 & ((cd.n >= 2) | next_is_head)) out.mx(slot) = hi0;
+  }
+  wave_sync();
+  n_out += heads_total;
+  if (m_has) last_id = rdlane_i(my_last_id, msb64(m_has));
+  return 0;
+}
+
 /* exact sequential replay of fpl:832-860 + push_piece on lane 0 (cold path) */
 template <class L, class S>
 PSD_NOINLINE int min_env_serial(L f1_, int n1_, L f2_, int n2_, L out_, int cap_, S s_, int K_) {
@@ -672,43 +865,8 @@ PSD_D int min_env_impl(L f1_, int n1_, L f2_, int n2_, L out_, int cap_, S s_, i
     }
     K = n1 + n2 - popc64(md & 0xffffffffull);
   } else {
-    int dup_before = 0; /* ends of f1 that are also ends of f2, among earlier chunks */
-    for (int base = 0; base < n1; base += WAVE) {
-      int i = base + lane;
-      bool valid = i < n1;
-      int p = 0;
-      bool dup = false;
-      if (valid) {
-        double x = f1.mx(i);
-        p = rank_mx(f2, n2, x);
-        dup = p < n2 && f2.mx(p) == x;
-      }
-      unsigned long long md = ballot(dup);
-      if (valid) {
-        int k = i + p - (dup_before + popc64(md & lanes_below(lane)));
-        if (k < iv_cap) s.iv(k) = (i << 16) | p;
-      }
-      dup_before += popc64(md);
-    }
-    int dup_total = dup_before;
-    dup_before = 0;
-    for (int base = 0; base < n2; base += WAVE) {
-      int j = base + lane;
-      bool valid = j < n2;
-      int q = 0;
-      bool dup = false;
-      if (valid) {
-        double x = f2.mx(j);
-        q = rank_mx(f1, n1, x);
-        dup = q < n1 && f1.mx(q) == x;
-      }
-      unsigned long long md = ballot(dup);
-      if (valid && !dup) {
-        int k = j + q - (dup_before + popc64(md & lanes_below(lane)));
-        if (k < iv_cap) s.iv(k) = (q << 16) | j;
-      }
-      dup_before += popc64(md);
-    }
+    const int dup_total = env_table_first(f1, n1, f2, n2, s, nullptr);
+    env_table_second(f1, n1, f2, n2, s, nullptr);
     K = n1 + n2 - dup_total;
   }
   /* (i1 << 16) | i2 in a signed int: both indices stay below 32768 (SPILL_CAP_MAX) */
@@ -717,117 +875,29 @@ PSD_D int min_env_impl(L f1_, int n1_, L f2_, int n2_, L out_, int cap_, S s_, i
   PSD_PROF_ADD(PROF_TABLE);
 
   /* ---- one lane per interval; ballot/prefix-scan compaction ---- */
-  int n_out = 0;
-  int err = 0;
-  bool need_serial = false;
-  /* source piece of the last candidate emitted so far, (list << 20) | index; carried across
-   * chunks */
-  int last_id = -1;
+  int n_out = 0, last_id = -1;
+  int status = 0;
   for (int base = 0; base < K; base += WAVE) {
-    int k = base + lane;
-    bool valid = k < K;
-    Cands cd;
-    cd.n = 0;
-    cd.first = 0;
-    cd.x1 = cd.x2 = 0.0;
-    double ia = 0.0, ib = 0.0;
-    Coef c1 = {0.0, 0.0, 0.0}, c2 = {0.0, 0.0, 0.0};
-    double prv1 = 0.0, prv2 = 0.0;
-    int di1 = 0, di2 = 0, i1 = 0, i2 = 0;
+    const int k = base + lane;
+    const bool valid = k < K;
+    EnvLane e;
     bool sl = false, sr = false;
     PSD_PROF_T0();
-    if (valid) {
-      int e = s.iv(k);
-      i1 = e >> 16;
-      i2 = e & 0xffff;
-      env_load_interval(f1, n1, f2, n2, i1, i2, c1, c2, ia, ib, err);
-      prv1 = f1.prv(i1);
-      di1 = f1.di(i1);
-      prv2 = f2.prv(i2);
-      di2 = f2.di(i2);
-    }
-    env_neighbour_flags(f1, f2, s, k, K, valid, valid && same_funs(c1, c2), sl, sr);
+    env_lane_load(f1, n1, f2, n2, s, k, valid, e);
+    env_neighbour_flags(f1, f2, s, k, K, valid, valid && same_funs(e.c1, e.c2), sl, sr);
     PSD_PROF_ADD(PROF_C_LOAD);
-    env_classify_lanes<HELP>(valid && err == 0, c1, c2, ia, ib, sl, sr, cd, chain, err, mth);
+    env_classify_lanes<HELP>(valid && e.err == 0, e.c1, e.c2, e.ia, e.ib, sl, sr, e.cd, chain, e.err,
+                             mth);
     PSD_PROF_ADD(PROF_CLASSIFY);
-    /* first / last candidate of this lane */
-    const int src0 = cd.first, src1 = cd.first ^ 1; /* the third piece has source src0 again */
-    Coef fc = src0 ? c2 : c1;
-    double fprv = src0 ? prv2 : prv1;
-    int fdi = src0 ? di2 : di1;
-    int lsrc = cd.n == 2 ? src1 : src0;
-    /* piece q of this interval spans [lo_q, hi_q] */
-    const double hi0 = cd.n == 1 ? ib : cd.x1;
-    const double hi1 = cd.n == 2 ? ib : cd.x2;
-    bool has = valid && cd.n > 0;
-    unsigned long long m_has = ballot(has);
-    unsigned long long m_err = ballot(err != 0);
-    if (m_err) {
-      int e = 0;
-      for (int l = 0; l < WAVE; l++) e |= shfl_i(err, l);
-      return -e;
-    }
-    /* predecessor = last candidate of the nearest lower lane that has one, else the carry.
-     * Only its identity crosses lanes; its fields are re-read from the input list. */
-    unsigned long long lb = lanes_below(lane);
-    unsigned long long below = m_has & lb;
-    const int my_last_id = (lsrc << 20) | (lsrc ? i2 : i1);
-    int pid = shfl_i(my_last_id, below ? msb64(below) : 0); /* per-lane source */
-    if (!below) pid = last_id;
-    const bool have_pred = pid >= 0;
-    /* (every lane reads a predecessor -- piece 0 where it has none -- and the tests are masked
-     * afterwards: one LDS round trip, no exec-masked region) */
-    const L &pl = (have_pred && (pid >> 20)) ? f2 : f1;
-    const int pi = have_pred ? (pid & 0xfffff) : 0;
-    const Coef pc = load_coef(pl, pi);
-    const double pprv = pl.prv(pi);
-    const int pdi = pl.di(pi);
-    const bool follows = has & have_pred;
-    const bool co = follows & coalesces(pc, pprv, pdi, fc, fprv, fdi);
-    const bool bi = bit_identical(pc, pprv, pdi, fc, fprv, fdi);
-    const bool head0 = !co; /* does the first candidate start a new output piece? */
-    const bool fuzzy = co & !bi;
-    /* candidates 2 and 3 of a lane alternate it1/it2 with same_funs(it1,it2) false, so
-     * they always start a new piece -- provided the run they follow is bit-identical to
-     * its head, which `fuzzy` checks. */
-    if (ballot(fuzzy)) {
-      need_serial = true;
-      break;
-    }
-    int heads = has ? ((head0 ? 1 : 0) + (cd.n - 1)) : 0;
-    unsigned long long hb0 = ballot((heads & 1) != 0);
-    unsigned long long hb1 = ballot((heads & 2) != 0);
-    int heads_before = popc64(hb0 & lb) + 2 * popc64(hb1 & lb);
-    int heads_total = popc64(hb0) + 2 * popc64(hb1);
-    if (n_out + heads_total > cap) return -WERR_OVERFLOW;
-    int slot = n_out + heads_before - (head0 ? 0 : 1); /* piece candidate 0 belongs to */
-    if (has & head0) store_piece(out, slot, fc, ia, hi0, fdi, fprv);
-    if (has & (cd.n >= 2)) {
-      Coef c = src1 ? c2 : c1;
-      store_piece(out, slot + 1, c, cd.x1, hi1, src1 ? di2 : di1, src1 ? prv2 : prv1);
-    }
-    if (has & (cd.n >= 3)) store_piece(out, slot + 2, fc, cd.x2, ib, fdi, fprv);
-    wave_sync();
-    /* a candidate that extends the previous piece only moves that piece's right end; of
-     * the members of a run only the last one (in this chunk) writes, after the heads. */
-    {
-      const unsigned long long m_head0 = ballot(has & head0);
-      const unsigned long long above = m_has & ~lb & ~(1ull << lane);
-      /* (bit 63 keeps ctz64 defined for the top lane of the run; it never is the lowest bit
-       * of a non-empty `above`) */
-      const bool next_is_head = !above | (((m_head0 >> ctz64(above | (1ull << 63))) & 1ull) != 0);
-      if (has & !head0 & ((cd.n >= 2) | next_is_head)) out.mx(slot) = hi0;
-    }
-    wave_sync();
-    n_out += heads_total;
-    if (m_has) last_id = rdlane_i(my_last_id, msb64(m_has));
+    status = env_compact_chunk(f1, f2, out, cap, valid, e, n_out, last_id);
     PSD_PROF_ADD(PROF_COMPACT);
-    if (SMALL) break; /* K <= 64: one chunk */
+    if (status < 0 || SMALL) break; /* SMALL: K <= 64, one chunk */
   }
+  if (status < 0 && status != -WERR_SERIAL) return status;
 #ifdef PSD_FORCE_SERIAL_ENV /* tests only: every envelope takes the sequential replay */
-  need_serial = true;
+  status = -WERR_SERIAL;
 #endif
-  if (need_serial) {
+  if (status == -WERR_SERIAL) {
     /* the specialised version leaves the replay (and the call it takes) to the general one */
     if (SMALL) return -WERR_SERIAL;
     if (lane == 0) g_sm.serial[wave_id()]++;

@@ -307,7 +307,7 @@ PSD_D void forward_body(const DeviceArgs &a) {
 #ifdef PSD_CALL_LDS_OPS /* throughput build: operations out of line (register budget) */
         n_new = chain_step<USE_HELPER>(a, cur, fn_index, chain, t,
                            lds_list(id_other_prev), n_other, lds_list(id_own_prev),
-                           n_own, lds_list(id_own_new), mlist, lsc, LDS_CAP,
+                           n_own, lds_list(id_own_new), mlist, lsc,
                            penalty / cum_weight_prev_i, cum_weight_prev_i, w, coverage,
                            cum_weight_new);
 #else

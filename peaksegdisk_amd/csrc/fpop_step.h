@@ -1,9 +1,10 @@
 /* fpop_step.h -- one chain's update for one data point.
  *
  * The accessors of a problem's slot of the HBM spill pool, the step in its three forms
- * (chain_step: operations out of line, lists in LDS or HBM; chain_step_fast: the usual case
- * inlined; chain_step_hbm: shared with the helper wave), data point 0, and moving a list
- * between LDS and HBM.
+ * (chain_step_ops: the skeleton, its three operations supplied by the caller; chain_step:
+ * operations out of line, lists in LDS or HBM; chain_step_fast: the usual case inlined;
+ * chain_step_hbm: shared with the helper wave), data point 0, and moving a list between LDS
+ * and HBM.
  *
  * Reached only through fpop_kernels.h: no include guard, compiled once per build variant into
  * namespace psd::PSD_VARIANT. */
@@ -66,28 +67,19 @@ PSD_D int step_tail(const DeviceArgs &a, ArenaCursor &cur, unsigned long long fn
  *   down_t = min_env(min_more(up_{t-1}),                    down_{t-1})  drv:324-349
  *   (t == 1: up_1 = the min-less result, down_1 = down_0)
  * then multiply, add the data point, multiply (drv:316-321,365-370).
- * Returns the new piece count or -(WERR_* bits). */
-template <bool HELP, class L, class S>
-PSD_D int chain_step(const DeviceArgs &a, ArenaCursor &cur, unsigned long long fn_index,
-                     int chain, int t, const L &other_prev, int n_other, const L &own_prev,
-                     int n_own, const L &own_new, const L &mlist, const S &sc, int cap,
-                     double pen_term, double cum_weight_prev, double w, int coverage,
-                     double cum_weight) {
+ * The three operations are the caller's: min_less() / min_more() leave their result in mlist
+ * (min-more at its far end) and return its piece count, min_env(nm) writes own_new; each
+ * returns -(WERR_* bits) on error.  Returns the new piece count or -(WERR_* bits). */
+template <class L, class Less, class More, class Env>
+PSD_D int chain_step_ops(const DeviceArgs &a, ArenaCursor &cur, unsigned long long fn_index,
+                         int chain, int t, const L &own_prev, int n_own, const L &own_new,
+                         const L &mlist, double cum_weight_prev, double w, int coverage,
+                         double cum_weight, Less &&min_less, More &&min_more, Env &&min_env) {
   int nm = 0;
-  /* operations out of line; in LDS the versions specialised for short functions when they
-   * apply */
-  /* (the specialised versions answer -WERR_SERIAL when they met a rare exp / log argument:
-   * their arithmetic has no branch for those, the general versions do) */
   if (chain == 0) {
-    nm = -WERR_SERIAL;
-    if (L::in_lds && n_other <= WAVE)
-      nm = uniform_i(min_less_small_wave(other_prev, n_other, mlist, cap, sc, t - 1, pen_term));
-    if (nm == -WERR_SERIAL) nm = min_less_wave(other_prev, n_other, mlist, cap, sc, t - 1, pen_term);
+    nm = min_less();
   } else if (t >= 2) {
-    nm = -WERR_SERIAL;
-    if (L::in_lds && n_other <= WAVE)
-      nm = uniform_i(min_more_small_wave(other_prev, n_other, mlist, cap, sc, t - 1));
-    if (nm == -WERR_SERIAL) nm = min_more_wave(other_prev, n_other, mlist, cap, sc, t - 1);
+    nm = min_more();
   }
   nm = uniform_i(nm); /* return values of out-of-line functions arrive in a VGPR */
   if (nm < 0) return nm;
@@ -101,17 +93,52 @@ PSD_D int chain_step(const DeviceArgs &a, ArenaCursor &cur, unsigned long long f
       n_new = n_own;
     }
   } else {
-    const L f1 = chain == 0 ? mlist : mlist.shifted(cap - nm);
-    n_new = -WERR_SERIAL;
-    if (L::in_lds && nm <= 32 && n_own <= 32)
-      n_new = uniform_i(
-          min_env_small_wave<HELP>(f1, nm, own_prev, n_own, own_new, cap, sc, chain));
-    if (n_new == -WERR_SERIAL) {
-      n_new = uniform_i(min_env_wave<HELP>(f1, nm, own_prev, n_own, own_new, cap, sc, chain));
-    }
+    n_new = uniform_i(min_env(nm));
   }
   if (n_new < 0) return n_new;
   return step_tail(a, cur, fn_index, own_new, n_new, cum_weight_prev, w, coverage, cum_weight);
+}
+
+/* The step with its operations out of line, one wave on lists in LDS or HBM. */
+template <bool HELP, class L, class S>
+PSD_D int chain_step(const DeviceArgs &a, ArenaCursor &cur, unsigned long long fn_index,
+                     int chain, int t, const L &other_prev, int n_other, const L &own_prev,
+                     int n_own, const L &own_new, const L &mlist, const S &sc, double pen_term,
+                     double cum_weight_prev, double w, int coverage, double cum_weight) {
+  /* (in LDS a constant here, not a captured value: the out-of-line operations are compiled for
+   * the one capacity they are ever called with) */
+  const int cap = L::in_lds ? LDS_CAP : a.spill_cap;
+  /* in LDS the versions specialised for short functions when they apply */
+  /* (the specialised versions answer -WERR_SERIAL when they met a rare exp / log argument:
+   * their arithmetic has no branch for those, the general versions do) */
+  return chain_step_ops(
+      a, cur, fn_index, chain, t, own_prev, n_own, own_new, mlist, cum_weight_prev, w, coverage,
+      cum_weight,
+      [&]() {
+        int nm = -WERR_SERIAL;
+        if (L::in_lds && n_other <= WAVE)
+          nm = uniform_i(min_less_small_wave(other_prev, n_other, mlist, cap, sc, t - 1, pen_term));
+        if (nm == -WERR_SERIAL)
+          nm = min_less_wave(other_prev, n_other, mlist, cap, sc, t - 1, pen_term);
+        return nm;
+      },
+      [&]() {
+        int nm = -WERR_SERIAL;
+        if (L::in_lds && n_other <= WAVE)
+          nm = uniform_i(min_more_small_wave(other_prev, n_other, mlist, cap, sc, t - 1));
+        if (nm == -WERR_SERIAL) nm = min_more_wave(other_prev, n_other, mlist, cap, sc, t - 1);
+        return nm;
+      },
+      [&](int nm) {
+        const L f1 = chain == 0 ? mlist : mlist.shifted(cap - nm);
+        int n_new = -WERR_SERIAL;
+        if (L::in_lds && nm <= 32 && n_own <= 32)
+          n_new = uniform_i(
+              min_env_small_wave<HELP>(f1, nm, own_prev, n_own, own_new, cap, sc, chain));
+        if (n_new == -WERR_SERIAL)
+          n_new = min_env_wave<HELP>(f1, nm, own_prev, n_own, own_new, cap, sc, chain);
+        return n_new;
+      });
 }
 
 /* The same update for the usual case -- data point t >= 2, lists in LDS, n_other <= 16 (so
@@ -170,7 +197,7 @@ PSD_COLD_DEV int chain_step_lds(const DeviceArgs &a, ArenaCursor &cur, unsigned 
   lsc.w = chain;
   return chain_step<HELP>(a, cur, fn_index, chain, t, lds_list(uniform_i(id_other_prev)),
                           uniform_i(n_other), lds_list(uniform_i(id_own_prev)), uniform_i(n_own),
-                          lds_list(uniform_i(id_own_new)), lds_list(4 + chain), lsc, LDS_CAP,
+                          lds_list(uniform_i(id_own_new)), lds_list(4 + chain), lsc,
                           uniform_d(pen_term), uniform_d(cum_weight_prev), uniform_d(w),
                           uniform_i(coverage), uniform_d(cum_weight));
 }
@@ -266,32 +293,22 @@ PSD_COLD_DEV int chain_step_hbm(const DeviceArgs &a, ArenaCursor &cur,
   const GlobalList own_new = global_list(a, p, uniform_i(id_own_new));
   const GlobalList mlist = global_list(a, p, 4 + chain);
   const GlobalScratch sc = global_scratch(a, p, chain);
-  int nm = 0;
-  if (chain == 0) {
-    nm = min_less_coop_wave(other_prev, n_other, mlist, cap, sc, t - 1, pen_term, chain, p,
-                            id_other_prev);
-  } else if (t >= 2) {
-    nm = min_more_coop_wave(other_prev, n_other, mlist, cap, sc, t - 1, chain, p, id_other_prev);
-  }
-  nm = uniform_i(nm);
-  if (nm < 0) return nm;
-  int n_new;
-  if (t == 1) {
-    if (chain == 0) {
-      copy_list_wave(mlist, nm, own_new);
-      n_new = nm;
-    } else {
-      copy_list_wave(own_prev, n_own, own_new);
-      n_new = n_own;
-    }
-  } else {
-    const int off1 = chain == 0 ? 0 : cap - nm;
-    n_new = uniform_i(min_env_coop_wave(mlist.shifted(off1), nm, own_prev, n_own, own_new, cap, sc,
-                                        chain, p, 4 + chain, off1, id_own_prev));
-  }
-  if (n_new < 0) return n_new;
-  return step_tail(a, cur, fn_index, own_new, n_new, uniform_d(cum_weight_prev), uniform_d(w),
-                   uniform_i(coverage), uniform_d(cum_weight));
+  return chain_step_ops(
+      a, cur, fn_index, chain, t, own_prev, n_own, own_new, mlist, uniform_d(cum_weight_prev),
+      uniform_d(w), uniform_i(coverage), uniform_d(cum_weight),
+      [&]() {
+        return min_less_coop_wave(other_prev, n_other, mlist, cap, sc, t - 1, pen_term, chain, p,
+                                  id_other_prev);
+      },
+      [&]() {
+        return min_more_coop_wave(other_prev, n_other, mlist, cap, sc, t - 1, chain, p,
+                                  id_other_prev);
+      },
+      [&](int nm) {
+        const int off1 = chain == 0 ? 0 : cap - nm;
+        return min_env_coop_wave(mlist.shifted(off1), nm, own_prev, n_own, own_new, cap, sc, chain,
+                                 p, 4 + chain, off1, id_own_prev);
+      });
 }
 #else
 /* The same step with every list in the HBM spill area (functions that outgrew LDS): a cold,
@@ -308,7 +325,7 @@ PSD_COLD_DEV int chain_step_hbm(const DeviceArgs &a, ArenaCursor &cur,
                            global_list(a, p, uniform_i(id_other_prev)), uniform_i(n_other),
                            global_list(a, p, uniform_i(id_own_prev)), uniform_i(n_own),
                            global_list(a, p, uniform_i(id_own_new)), global_list(a, p, 4 + chain),
-                           global_scratch(a, p, chain), a.spill_cap, uniform_d(pen_term),
+                           global_scratch(a, p, chain), uniform_d(pen_term),
                            uniform_d(cum_weight_prev), uniform_d(w), uniform_i(coverage),
                            uniform_d(cum_weight));
 }

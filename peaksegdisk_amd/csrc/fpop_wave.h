@@ -33,8 +33,9 @@
  * ends with the out-of-line wrappers.
  *   fpop_lds.h       LDS layout, helper mailbox, profiling macros, list accessors
  *   fpop_walks.h     first pass, min_less_impl, min_more_impl
- *   fpop_envelope.h  min_env_impl and its sequential replay
- *   fpop_coop.h      the helper wave's loop; the envelope of lists in HBM by two waves
+ *   fpop_envelope.h  interval table, chunk load, classification, compaction (env_compact) --
+ *                    each once, for every envelope; min_env_impl and its sequential replay
+ *   fpop_coop.h      the helper wave's loop; how two waves share the chunks of an envelope in HBM
  */
 #include "fpop_types.h"
 

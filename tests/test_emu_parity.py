@@ -118,34 +118,45 @@ def test_emu_sequential_envelope_replay(oracle_det, tmp_path):
     from peaksegdisk_amd import _native, synthetic
     from peaksegdisk_amd.grid import ProblemSet
     subprocess.run(["make", "-s", "-C", EMU_DIR, "all"], check=True)
-    cs, ce, cnt = synthetic.poisson_coverage(1000, seed=31)
-    pens = ["0.7", "60", "5000"]
-    bg = str(tmp_path / "coverage.bedGraph")
-    synthetic.write_bedgraph(bg, cs, ce, cnt)
+    # the second data set puts the lists in HBM (lat: the chain wave and its helper share the
+    # chunks of an envelope): the replay on lists in HBM, and the way out of the shared envelope
+    # that waits for the helper first.  At penalty 10000 the functions pass 256 merged intervals,
+    # i.e. more than four chunks: chunks of either wave, and the carry across chunks.
+    data_sets = [("poisson", synthetic.poisson_coverage(1000, seed=31), ["0.7", "60", "5000"]),
+                 ("increasing", synthetic.increasing_coverage(600), ["100", "10000"])]
+    for name, (cs, ce, cnt), pens in data_sets:
+        synthetic.write_bedgraph(str(tmp_path / (name + ".bedGraph")), cs, ce, cnt)
     # ... and the other hand-over nothing realistic triggers: a step whose exp/log met a rare
     # argument (the specialised path evaluates them without the branch for those) is redone by
     # the general path; forced for every step with -DPSD_FORCE_RARE
     for variant, build in (("serial", "lat"), ("serial", "thr"), ("rare", "lat"), ("rare", "thr")):
         lib = _native.declare(ctypes.CDLL(os.path.join(EMU_DIR, "_build",
                                                        "libpeaksegdisk_emu_%s.so" % variant)))
-        os.environ["PEAKSEG_HIP_VARIANT"] = build
-        try:
-            pset = ProblemSet([(cnt, (ce - cs).astype(np.int32))],
-                              [(0, float(p)) for p in pens], lib=lib)
-            pset.solve()
-        finally:
-            del os.environ["PEAKSEG_HIP_VARIANT"]
-        assert pset.kernel_build == build
-        for i, pen in enumerate(pens):
-            r = pset.result(i)
-            assert r.status == 0 and (r.n_serial_env > 0 or variant == "rare")
-            want = str(tmp_path / ("o_%d.db" % i))
-            if not os.path.exists(want):
-                assert oracle_det.solve(bg, pen, want) == 0
-            got = str(tmp_path / ("g_%s_%s_%d.db" % (variant, build, i)))
-            pset.export_db(i, ce, got)
-            assert open(got, "rb").read() == open(want, "rb").read(), (variant, build, pen)
-        pset.close()
+        for name, (cs, ce, cnt), pens in data_sets:
+            if name == "increasing" and variant != "serial":
+                continue
+            bg = str(tmp_path / (name + ".bedGraph"))
+            os.environ["PEAKSEG_HIP_VARIANT"] = build
+            try:
+                pset = ProblemSet([(cnt, (ce - cs).astype(np.int32))],
+                                  [(0, float(p)) for p in pens], lib=lib)
+                pset.solve()
+            finally:
+                del os.environ["PEAKSEG_HIP_VARIANT"]
+            assert pset.kernel_build == build
+            for i, pen in enumerate(pens):
+                r = pset.result(i)
+                assert r.status == 0 and (r.n_serial_env > 0 or variant == "rare")
+                if name == "increasing" and pen == "10000":
+                    assert r.spill_steps > 0 and r.max_intervals > 256
+                want = str(tmp_path / ("o_%s_%d.db" % (name, i)))
+                if not os.path.exists(want):
+                    assert oracle_det.solve(bg, pen, want) == 0
+                got = str(tmp_path / ("g_%s_%s_%s_%d.db" % (variant, build, name, i)))
+                pset.export_db(i, ce, got)
+                assert open(got, "rb").read() == open(want, "rb").read(), (variant, build, name,
+                                                                           pen)
+            pset.close()
 
 
 def test_emu_varied_data_shapes(psd, oracle_det, tmp_path, monkeypatch):

@@ -379,10 +379,15 @@ def test_sequential_envelope_replay(psd, oracle_det, tmp_path):
     from conftest import ROOT
     from peaksegdisk_amd import ProblemSet, _native, synthetic
     csrc = os.path.join(ROOT, "peaksegdisk_amd", "csrc")
-    cs, ce, cnt = synthetic.poisson_coverage(5000, seed=31)
-    pens = ["0.7", "60", "5000"]
-    bg = str(tmp_path / "coverage.bedGraph")
-    synthetic.write_bedgraph(bg, cs, ce, cnt)
+    # the second data set puts the lists in HBM, where the chain wave and its helper share the
+    # chunks of an envelope (default build: lat): the replay on lists in HBM, and the way out of
+    # the shared envelope that waits for the helper first.  At penalty 10000 the functions pass
+    # 256 merged intervals, i.e. more than four chunks: chunks of either wave, and the carry
+    # across chunks.
+    data_sets = [("poisson", synthetic.poisson_coverage(5000, seed=31), ["0.7", "60", "5000"]),
+                 ("increasing", synthetic.increasing_coverage(600), ["100", "10000"])]
+    for name, (cs, ce, cnt), pens in data_sets:
+        synthetic.write_bedgraph(str(tmp_path / (name + ".bedGraph")), cs, ce, cnt)
     # the same for the other hand-over that nothing realistic triggers: a step whose exp / log
     # met a rare argument (the specialised step evaluates them without the branch for those)
     # is redone by the general step; forced for every step with -DPSD_FORCE_RARE
@@ -396,19 +401,26 @@ def test_sequential_envelope_replay(psd, oracle_det, tmp_path):
     for variant, (lib_path, proc) in procs.items():
         assert proc.wait() == 0
         lib = _native.declare(ctypes.CDLL(lib_path))
-        pset = ProblemSet([(cnt, (ce - cs).astype(np.int32))], [(0, float(p)) for p in pens],
-                          lib=lib)
-        pset.solve()
-        for i, pen in enumerate(pens):
-            r = pset.result(i)
-            assert r.status == 0 and (r.n_serial_env > 0 or variant == "rare")
-            want = str(tmp_path / ("o_%d.db" % i))
-            if not os.path.exists(want):
-                assert oracle_det.solve(bg, pen, want) == 0
-            got = str(tmp_path / ("g_%s_%d.db" % (variant, i)))
-            pset.export_db(i, ce, got)
-            assert open(got, "rb").read() == open(want, "rb").read(), (variant, pen)
-        pset.close()
+        for name, (cs, ce, cnt), pens in data_sets:
+            if name == "increasing" and variant != "serial":
+                continue
+            bg = str(tmp_path / (name + ".bedGraph"))
+            pset = ProblemSet([(cnt, (ce - cs).astype(np.int32))], [(0, float(p)) for p in pens],
+                              lib=lib)
+            pset.solve()
+            assert name != "increasing" or pset.kernel_build == "lat"
+            for i, pen in enumerate(pens):
+                r = pset.result(i)
+                assert r.status == 0 and (r.n_serial_env > 0 or variant == "rare")
+                if name == "increasing" and pen == "10000":
+                    assert r.spill_steps > 0 and r.max_intervals > 256
+                want = str(tmp_path / ("o_%s_%d.db" % (name, i)))
+                if not os.path.exists(want):
+                    assert oracle_det.solve(bg, pen, want) == 0
+                got = str(tmp_path / ("g_%s_%s_%d.db" % (variant, name, i)))
+                pset.export_db(i, ce, got)
+                assert open(got, "rb").read() == open(want, "rb").read(), (variant, name, pen)
+            pset.close()
 
 
 def check_grid_properties(pset, pens, cs, ce, cnt, n_bins):
