@@ -157,6 +157,17 @@ def test_emu_sequential_envelope_replay(oracle_det, tmp_path):
                 assert open(got, "rb").read() == open(want, "rb").read(), (variant, build, name,
                                                                            pen)
             pset.close()
+        # third data set, as in the GPU test
+        os.environ["PEAKSEG_HIP_VARIANT"] = build
+        try:
+            assert gp.check_branch_fixture_stores(lib, oracle_det, tmp_path, (variant, build)) > 0
+        finally:
+            del os.environ["PEAKSEG_HIP_VARIANT"]
+
+
+def test_emu_reference_branch_fixture(psd, oracle_det, tmp_path, monkeypatch):
+    import test_gpu_reference_branches as gb
+    gb.test_reference_branch_fixture(psd, oracle_det, tmp_path, monkeypatch)
 
 
 def test_emu_varied_data_shapes(psd, oracle_det, tmp_path, monkeypatch):

@@ -368,6 +368,31 @@ def test_varied_data_shapes(psd, oracle_det, tmp_path, monkeypatch, n_cases, see
         monkeypatch.delenv("PEAKSEG_HIP_VARIANT")
 
 
+def check_branch_fixture_stores(lib, oracle_det, tmp_path, tag):
+    """The problems of tests/golden/reference_branches.json (inputs that take the outcomes of the
+    piece algebra no other input takes: two crossings with the second function first, ...), one
+    contig each, solved by `lib`: every stored function against the oracle's."""
+    import reference_live as rl
+    from peaksegdisk_amd import ProblemSet
+    cases = rl.load_branch_fixture()["cases"]
+    pset = ProblemSet([(np.array(c["count"], dtype=np.int32),
+                        (np.array(c["chromEnd"]) - np.array(c["chromStart"])).astype(np.int32))
+                       for c in cases], [(k, float(c["penalty"])) for k, c in enumerate(cases)], lib=lib)
+    pset.solve()
+    for k, case in enumerate(cases):
+        bg = str(tmp_path / ("branch_%d.bedGraph" % k))
+        want = bg + ".db"
+        if not os.path.exists(want):
+            open(bg, "w").write(rl.case_text(case))
+            assert oracle_det.solve(bg, case["penalty"], want) == 0
+        assert pset.result(k).status == 0, (tag, case["name"])
+        got = str(tmp_path / "branch_got.db")
+        pset.export_db(k, np.array(case["chromEnd"], dtype=np.int32), got)
+        assert open(got, "rb").read() == open(want, "rb").read(), (tag, case["name"])
+    pset.close()
+    return len(cases)
+
+
 @GPU
 def test_sequential_envelope_replay(psd, oracle_det, tmp_path):
     """The sequential replay of min_env (min_env_serial) and the way the latency build's
@@ -421,6 +446,9 @@ def test_sequential_envelope_replay(psd, oracle_det, tmp_path):
                 pset.export_db(i, ce, got)
                 assert open(got, "rb").read() == open(want, "rb").read(), (variant, name, pen)
             pset.close()
+        # third data set: the replay's own copy of the two-crossing choice, and the other rare
+        # outcomes of the piece algebra
+        assert check_branch_fixture_stores(lib, oracle_det, tmp_path, variant) > 0
 
 
 def check_grid_properties(pset, pens, cs, ce, cnt, n_bins):
