@@ -42,6 +42,11 @@ extern "C" {
                                       that sum to 2^31 or more in a contig; the contig, the read and
                                       the reason are in peakseg_hip_last_error() */
 
+#define ERROR_LABEL_ARGUMENTS 19   /* labels that cannot be counted: a negative number of labels, a
+                                      NULL or misaligned array, a label with chromStart >= chromEnd
+                                      or an annotation code outside 0..3; the contig, the label's
+                                      index and the reason are in peakseg_hip_last_error() */
+
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
  *                               per GPU sets it from its rank
@@ -412,6 +417,48 @@ int peakseg_hip_problem_set_packed_segment_stats_download(psd_problem_set *set, 
 int peakseg_hip_segment_stats_tile_runs(void);
 /* milliseconds (HIP events) of the calling thread's last pack_segment_stats: zeroing and launches */
 int peakseg_hip_segment_stats_last_ms(float *ms);
+
+/* The label errors of every problem of a solved set made from dense counts or reads, counted on
+ * the device from the resident segment tables (the PeakError convention; coordinates are BED
+ * coordinates, 0-based and half-open).  A label is [chromStart, chromEnd) with an annotation code:
+ * 0 noPeaks, 1 peakStart, 2 peakEnd, 3 peaks; a peak is an odd row [ps, pe) of the segments table.
+ *   noPeaks, peaks  count = peaks with ps < chromEnd && chromStart < pe
+ *   peakStart       count = peaks with chromStart <= ps < chromEnd
+ *   peakEnd         count = peaks with chromStart < pe <= chromEnd
+ * false positive: noPeaks with count >= 1, peakStart / peakEnd with count >= 2; false negative:
+ * peaks / peakStart / peakEnd with count == 0.  Labels come in any order, may overlap, and may lie
+ * partly or wholly outside the contig.
+ * first_chromStart: one per CONTIG, NULL = zeros (the check of pack_segments).  n_labels[c]: the
+ * labels of contig c; label_start / label_end / label_annotation: per contig an int32 array of that
+ * many entries (not read where n_labels[c] == 0); labels_on_device != 0: the arrays are device
+ * addresses (multiples of 4) and are read in place, else host memory that the library uploads.
+ * rows_out[p] (n_problems entries, host, may be NULL) receives problem p's row count: its contig's
+ * label count.  The packed columns count / fp / fn (int32) hold the problems' rows one problem
+ * after the other, in the order of the labels as given; totals holds five int32 per problem:
+ * errors, fp, fn, possible_fp (labels that are not peaks), possible_fn (labels that are not
+ * noPeaks).  Integer arithmetic only: the same whatever the schedule.
+ * Returns the total number of rows; -1 for a set that is not solved or was not made from dense
+ * counts; -ERROR_LABEL_ARGUMENTS for what that status names (host arrays are checked on the host,
+ * device arrays by the first launch, after which nothing further is launched); the text is in
+ * peakseg_hip_last_error.  The device addresses stay valid until the set is solved again, this
+ * function is called again, or the set is destroyed; ..._download copies the columns and the
+ * totals (any may be NULL) to host arrays and returns -1 when there is nothing packed. */
+long long peakseg_hip_problem_set_pack_label_errors(
+    psd_problem_set *set, const int *first_chromStart, const long long *n_labels,
+    const int *const *label_start, const int *const *label_end, const int *const *label_annotation,
+    int labels_on_device, long long *rows_out, const int **count_dev, const int **fp_dev,
+    const int **fn_dev, const int **totals_dev);
+int peakseg_hip_problem_set_packed_label_errors_download(psd_problem_set *set, int *count_out,
+                                                         int *fp_out, int *fn_out, int *totals_out);
+/* milliseconds (HIP events) of the calling thread's last pack_label_errors: zeroing and launches */
+int peakseg_hip_label_errors_last_ms(float *ms);
+
+/* Where a round of the parallel penalty search looks besides its secant penalty: up to `extras`
+ * penalties between over_penalty (the bracket's smaller penalty, 0 allowed) and under_penalty (its
+ * larger one, +Inf allowed) into out[extras]; returns how many.  The caller keeps what survives
+ * the 15-digit string strictly inside the bracket. */
+int peakseg_hip_search_place_penalties(double under_penalty, double over_penalty, double secant,
+                                       int extras, double *out);
 
 /* The ten fields of the reference's loss.tsv row of one solved problem, in its order and with its
  * arithmetic: penalty, segments, peaks, bases, bedGraph.lines, mean.pen.cost, total.loss,

@@ -15,6 +15,7 @@ ERROR_DEVICE_SOLVER = 13
 ERROR_DEVICE_MEMORY = 14
 ERROR_DENSE_ARGUMENTS = 17
 ERROR_READS_ARGUMENTS = 18
+ERROR_LABEL_ARGUMENTS = 19
 
 
 class PsdResult(ctypes.Structure):
@@ -204,6 +205,19 @@ def declare(lib):
     lib.peakseg_hip_reads_pileup_probe.restype = c.c_int
     lib.peakseg_hip_reads_last_pileup_ms.argtypes = [c.POINTER(c.c_float), c.POINTER(c.c_float)]
     lib.peakseg_hip_reads_last_pileup_ms.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_label_errors.argtypes = [
+        c.c_void_p, c.c_void_p, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p), c.POINTER(c.c_void_p), c.c_int, c.c_void_p, c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p), c.POINTER(c.c_void_p), c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_pack_label_errors.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_label_errors_download.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_problem_set_packed_label_errors_download.restype = c.c_int
+    lib.peakseg_hip_label_errors_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_label_errors_last_ms.restype = c.c_int
+    lib.peakseg_hip_search_place_penalties.argtypes = [
+        c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
+    lib.peakseg_hip_search_place_penalties.restype = c.c_int
     return lib
 
 
@@ -235,6 +249,9 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_segment_stats_tile_runs", "peakseg_hip_segment_stats_last_ms",
     "peakseg_hip_problem_set_create_reads", "peakseg_hip_reads_pileup_probe",
     "peakseg_hip_reads_last_pileup_ms",
+    "peakseg_hip_problem_set_pack_label_errors",
+    "peakseg_hip_problem_set_packed_label_errors_download",
+    "peakseg_hip_label_errors_last_ms", "peakseg_hip_search_place_penalties",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -349,10 +349,60 @@ def _penalty_lists(penalties, n_contigs, noun):
     return pens
 
 
-def _solve_dense_set(make_set, pens, chrom, stats, single, label):
+LABEL_STATUS = ("correct", "false positive", "false negative")
+
+
+def _label_lists(labels, n_contigs, single, noun):
+    """`labels` of PeakSegFPOP_dense / PeakSegFPOP_reads / the target-interval entries -> one
+    (chromStart, chromEnd, annotation codes) of host int32 arrays per contig.  A single contig
+    takes its entry bare; None or an empty entry is a contig without labels."""
+    from .grid import annotation_codes
+    if single:
+        labels = [labels]
+    if len(labels) != n_contigs:
+        raise ValueError("labels: one entry per %s (%d entries, %d %ss)"
+                         % (noun, len(labels), n_contigs, noun))
+    out = []
+    for c, entry in enumerate(labels):
+        if entry is None or len(entry) == 0:
+            out.append(tuple(np.zeros(0, dtype=np.int32) for _ in range(3)))
+            continue
+        if len(entry) != 3:
+            raise ValueError("labels: %s %d is not (chromStart, chromEnd, annotation)" % (noun, c))
+        codes = annotation_codes(entry[2], "labels: %s %d" % (noun, c))
+        cols = []
+        for v in (entry[0], entry[1], codes):
+            if hasattr(v, "data_ptr"):
+                v = v.cpu().numpy()
+            cols.append(_int32_vector(v, "labels"))
+        if not (len(cols[0]) == len(cols[1]) == len(cols[2])):
+            raise ValueError("labels: %s %d: columns of different lengths" % (noun, c))
+        out.append(tuple(cols))
+    return out
+
+
+def _label_frame(chrom, entry, columns):
+    """the .label_errors data frame of one model: the contig's labels and what the model does"""
+    from .grid import ANNOTATIONS
+    count, fp, fn = columns
+    status = np.where(fp != 0, LABEL_STATUS[1], np.where(fn != 0, LABEL_STATUS[2], LABEL_STATUS[0]))
+    return pd.DataFrame({
+        "chrom": chrom, "chromStart": entry[0], "chromEnd": entry[1],
+        "annotation": np.array(ANNOTATIONS, dtype=object)[entry[2]] if len(entry[2]) else
+        np.zeros(0, dtype=object),
+        "count": count, "fp": fp, "fn": fn, "status": status},
+        columns=["chrom", "chromStart", "chromEnd", "annotation", "count", "fp", "fn", "status"])
+
+
+LABEL_TOTALS = ["errors", "fp", "fn", "possible.fp", "possible.fn"]
+
+
+def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None):
     """What PeakSegFPOP_dense and PeakSegFPOP_reads share: the problems of `pens` (one list per
     contig), the set -- make_set(problems) -> (ProblemSet, chromStart of each contig's first
     base) --, its solution, and the reference's data frames, nested as `pens` is."""
+    if labels is not None:
+        labels = _label_lists(labels, len(pens), single, "contig")
     problems, pen_strs = [], []
     for c, q in enumerate(pens):
         for pen_num in q:
@@ -375,6 +425,11 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label):
             raise PeakSegError(_native.ERROR_DEVICE_SOLVER, str(e))
         columns = pset.segment_columns(first_chromStart=chrom_starts)
         seg_stats = pset.segment_stats(first_chromStart=chrom_starts) if stats else None
+        if labels is not None:
+            try:
+                label_totals, label_cols = pset.label_errors(labels, first_chromStart=chrom_starts)
+            except RuntimeError as e:
+                raise PeakSegError(getattr(e, "status", _native.ERROR_DEVICE_SOLVER), str(e))
         rows = [(pset.loss(p), pset.result(p)) for p in range(len(problems))]
     finally:
         pset.close()
@@ -403,6 +458,10 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label):
         if stats:
             flat[-1].stats = pd.DataFrame(dict(zip(
                 ["reads", "max.count", "summitStart", "summitEnd"], seg_stats[p])))
+        if labels is not None:
+            flat[-1].label_errors = _label_frame(chrom, labels[c], label_cols[p])
+            for name, value in zip(LABEL_TOTALS, label_totals[p].tolist()):
+                flat[-1].loss[name] = value
     out, o = [], 0
     for q in pens:
         out.append(flat[o:o + len(q)])
@@ -411,7 +470,7 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label):
 
 
 def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=None, device=0,
-                      stats=False):
+                      stats=False, labels=None):
     """PeakSegFPOP_vec without its files: dense integer coverage (one count per base) is
     run-length encoded and solved on the GPU, and the reference's result comes back as data
     frames.  count_vecs: one vector or a list of them (int32 numpy arrays or torch tensors are
@@ -424,7 +483,13 @@ def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=No
     stats=True: every result also gets .stats, a data frame with one row per row of .segments and
     the columns reads (the sum of the segment's bases' counts), max.count, summitStart and
     summitEnd (the first run of the segment whose count is max.count), computed on the GPU from
-    the resident runs (ProblemSet.segment_stats)."""
+    the resident runs (ProblemSet.segment_stats).
+    labels: per vector (bare for a single vector) its labels (chromStart, chromEnd, annotation) --
+    annotation a list of noPeaks / peakStart / peakEnd / peaks or their codes 0..3 --, None for a
+    vector without labels: every result also gets .label_errors, a data frame chrom, chromStart,
+    chromEnd, annotation, count, fp, fn, status (correct / false positive / false negative) with
+    one row per label, counted on the GPU (ProblemSet.label_errors), and $loss the columns errors,
+    fp, fn, possible.fp and possible.fn."""
     from .grid import ProblemSet
     single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
         len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
@@ -439,7 +504,7 @@ def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=No
         raise ValueError("chrom.starts: one per vector")
     return _solve_dense_set(
         lambda problems: (ProblemSet.from_dense(contigs, problems, device=device), chrom_starts),
-        pens, chrom, stats, single, "<dense counts>")
+        pens, chrom, stats, single, "<dense counts>", labels)
 
 
 # ---- aligned reads in memory (additive: the pile-up happens on the GPU) -----------------------
@@ -455,7 +520,7 @@ def _read_contigs(reads):
 
 
 def PeakSegFPOP_reads(reads, penalties, chrom="chrUnknown", extents=None, bases_counted="each",
-                      device=0, stats=False):
+                      device=0, stats=False, labels=None):
     """PeakSegFPOP_dense with the step in front of it: aligned reads are piled up into coverage,
     run-length encoded and solved on the GPU.  reads: one contig -- (chromStart, chromEnd) or
     (chromStart, chromEnd, count), one entry per read, in any order -- or a list of contigs
@@ -464,7 +529,7 @@ def PeakSegFPOP_reads(reads, penalties, chrom="chrUnknown", extents=None, bases_
     per contig; extents: per contig (a single pair for a single contig) the (chromStart, chromEnd)
     whose bases are the data, default (min chromStart, max chromEnd) of its reads;
     bases_counted: "each" base of a read or only its "end".  Coordinates are genomic: base 0 of a
-    contig is its extent's chromStart.  Results and `stats` as PeakSegFPOP_dense."""
+    contig is its extent's chromStart.  Results, `stats` and `labels` as PeakSegFPOP_dense."""
     from .grid import ProblemSet
     single, contigs = _read_contigs(reads)
     names = ("chromStart", "chromEnd", "count")
@@ -478,7 +543,77 @@ def PeakSegFPOP_reads(reads, penalties, chrom="chrUnknown", extents=None, bases_
         pset = ProblemSet.from_reads(contigs, problems, extents=extents,
                                      bases_counted=bases_counted, device=device)
         return pset, pset.contig_starts
-    return _solve_dense_set(make_set, pens, chrom, stats, single, "<aligned reads>")
+    return _solve_dense_set(make_set, pens, chrom, stats, single, "<aligned reads>", labels)
+
+
+# ---- the target interval of labelled contigs (additive) ---------------
+
+def _target_interval(make_set, n_contigs, labels, width, max_rounds, single, label):
+    from . import target
+    labels = _label_lists(labels, n_contigs, single, "contig")
+    if not (isinstance(max_rounds, (int, np.integer)) and max_rounds >= 1):
+        raise ValueError("max_rounds: a positive integer")
+
+    def make(problems):
+        try:
+            return make_set(problems)
+        except RuntimeError as e:
+            status = getattr(e, "status", _native.ERROR_DEVICE_SOLVER)
+            if status == _native.ERROR_DEVICE_MEMORY:
+                raise
+            msg = _native.status_message(status, label, "", "")
+            detail = _native.last_error()
+            raise PeakSegError(status, "%s (%s)" % (msg, detail) if detail else msg)
+    out = target.target_interval(make, n_contigs, labels, _check_width(width), int(max_rounds))
+    return out[0] if single else out
+
+
+def targetInterval_dense(count_vecs, labels, width=None, max_rounds=20, chrom_starts=None,
+                         device=0):
+    """The target interval of labelled coverage: for every vector the interval of log(penalty)
+    whose models have the fewest label errors, the target of a penalty-learning regression.
+    count_vecs, chrom_starts and device as PeakSegFPOP_dense, labels as its `labels`.  The vectors
+    stay resident on the GPU as one problem set with `width` models per vector (None: 8; 1 to
+    256), and every round solves what all the searches ask for in one launch and counts the label
+    errors of all models on the device.  Returns, for a single vector, a target.TargetInterval,
+    else a list of them: min_log_lambda, max_log_lambda (+-inf where the interval has no end),
+    lower_exact, upper_exact (the limit is the breakpoint between two neighbouring models, or
+    infinite), min_errors, rounds, and models, a data frame penalty, peaks, total.loss, errors,
+    fp, fn, round with one row per solved penalty."""
+    from .grid import ProblemSet
+    single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
+        len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
+    vecs = [count_vecs] if single else list(count_vecs)
+    if len(vecs) == 0:
+        raise ValueError("count.vecs must hold at least one vector")
+    contigs = [_int32_vector(v) for v in vecs]
+    if chrom_starts is None:
+        chrom_starts = [0] * len(vecs)
+    if len(chrom_starts) != len(vecs):
+        raise ValueError("chrom.starts: one per vector")
+    return _target_interval(
+        lambda problems: (ProblemSet.from_dense(contigs, problems, device=device), chrom_starts),
+        len(vecs), labels, width, max_rounds, single, "<dense counts>")
+
+
+def targetInterval_reads(reads, labels, width=None, max_rounds=20, extents=None,
+                         bases_counted="each", device=0):
+    """targetInterval_dense with the pile-up in front of it: reads, extents and bases_counted as
+    PeakSegFPOP_reads, the rest and the result as targetInterval_dense."""
+    from .grid import ProblemSet
+    single, contigs = _read_contigs(reads)
+    names = ("chromStart", "chromEnd", "count")
+    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
+               if isinstance(entry, (tuple, list)) else entry for entry in contigs]
+    if single and extents is not None:
+        extents = [extents]
+
+    def make_set(problems):
+        pset = ProblemSet.from_reads(contigs, problems, extents=extents,
+                                     bases_counted=bases_counted, device=device)
+        return pset, pset.contig_starts
+    return _target_interval(make_set, len(contigs), labels, width, max_rounds, single,
+                            "<aligned reads>")
 
 
 def coverage_from_reads(chromStart, chromEnd, count=None, chrom="chrUnknown", extent=None,

@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, reads, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, labels, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -82,6 +82,8 @@
 #include "segment_stats.h"
 /* coverage from aligned reads: the pile-up the dense encoder reads in place */
 #include "reads_pileup.h"
+/* label errors of every model from the resident tables */
+#include "label_errors.h"
 
 #include <ctype.h>
 #include <errno.h>
@@ -117,6 +119,7 @@
 #include "peakseg_pack.h"
 #include "peakseg_dense.h"
 #include "peakseg_reads.h"
+#include "peakseg_labels.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -163,6 +166,8 @@ extern "C" void peakseg_hip_problem_set_destroy(psd_problem_set *s) {
     if (e) (void)hipEventDestroy(e);
   if (s->ev2) (void)hipEventDestroy(s->ev2);
   for (auto &e : s->stats.ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto &e : s->labels.ev)
     if (e) (void)hipEventDestroy(e);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   if (s->stream2) (void)hipStreamDestroy(s->stream2);
@@ -472,6 +477,10 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
                 "error code %d: aligned reads that cannot be piled up (an empty or negative extent, a "
                 "read with chromStart >= chromEnd or a negative count, or counts that sum to 2^31 or "
                 "more in a contig)", status);
+    PSD_MESSAGE(ERROR_LABEL_ARGUMENTS,
+                "error code %d: labels that cannot be counted (a negative number of labels, a NULL or "
+                "misaligned array, a label with chromStart >= chromEnd or an annotation code outside "
+                "0..3)", status);
     default:
       snprintf(buf, buf_len, "error code %d", status);
       break;

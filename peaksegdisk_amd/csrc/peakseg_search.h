@@ -49,6 +49,24 @@ void place_penalties(const psd_search_row &under, const psd_search_row &over, do
   }
 }
 
+}  // namespace
+
+extern "C" int peakseg_hip_search_place_penalties(double under_penalty, double over_penalty,
+                                                  double secant, int extras, double *out) {
+  if (extras <= 0 || !out) return 0;
+  psd_search_row under{}, over{};
+  under.penalty = under_penalty;
+  over.penalty = over_penalty;
+  std::vector<double> more;
+  place_penalties(under, over, secant, extras, more);
+  int n = 0;
+  for (double pen : more)
+    if (n < extras) out[n++] = pen;
+  return n;
+}
+
+namespace {
+
 /* What tells the sequential entries from the parallel ones: the words of their error texts and
  * of their PEAKSEG_HIP_TIMING lines. */
 struct SearchWords {

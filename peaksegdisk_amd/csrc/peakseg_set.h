@@ -22,6 +22,7 @@ struct SolveRun {
   unsigned long long park_pool_pieces = 0; /* ... and what they took from the overflow pool */
   long long pack_total = -1, segs_total = -1; /* rows of the packed tables (-1: not packed) */
   long long stats_total = -1;                 /* ... and of the packed segment statistics */
+  long long labels_total = -1;                /* ... and of the packed label errors */
 };
 
 /* Segment tables packed at their exact sizes (peakseg_pack.h): up to three columns and, per
@@ -44,6 +45,23 @@ struct StatsTable {
   int *d_tile_problem = nullptr;
   long long n_tiles = 0;
   std::vector<long long> tile0; /* first tile of every problem */
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+/* What peakseg_hip_problem_set_pack_label_errors keeps (peakseg_labels.h): the labels of a call
+ * with host arrays, the per-contig and per-problem descriptors, what translate_kernel leaves for
+ * count_kernel, the contigs' check words, and the packed columns with the problems' totals.  Every
+ * array grows to what the largest call so far needed. */
+struct LabelTable {
+  int *d_labels = nullptr;             /* 3 x labels: start, end, annotation (host arrays only) */
+  psd::labels::Contig *d_contigs = nullptr; /* per contig */
+  long long *d_lab_off = nullptr;      /* n_contigs + 1 */
+  unsigned long long *d_check = nullptr; /* per contig */
+  long long *d_desc = nullptr;         /* psd::labels::DESC per problem */
+  int *totals = nullptr;               /* psd::labels::TOTALS per problem */
+  psd::labels::Quad *where = nullptr;  /* per label: what translate_kernel leaves */
+  int *count = nullptr, *fp = nullptr, *fn = nullptr; /* per packed row */
+  long long label_capacity = 0, row_capacity = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
@@ -109,6 +127,7 @@ struct psd_problem_set {
    * mean) */
   PackedTable pack, segs;
   StatsTable stats; /* (sets made from dense counts) */
+  LabelTable labels; /* (sets made from dense counts) */
 
   /* Sets made from dense counts (peakseg_hip_problem_set_create_dense): run_end[] next to count[]
    * and weight[], the sum of each contig's counts, and which contigs are constant.  Their trivial

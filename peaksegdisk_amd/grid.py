@@ -38,6 +38,55 @@ def _dense_pointer(k, v, device, what="from_dense: contig %d"):
                      % (what, type(v).__name__))
 
 
+ANNOTATIONS = ("noPeaks", "peakStart", "peakEnd", "peaks")  # the codes of label_errors
+
+
+def annotation_codes(annotation, what="labels"):
+    """the annotation column as label_errors passes it on: int32 arrays and tensors as they are, a
+    list of the four strings as its codes; ValueError names an unknown string and its index"""
+    if isinstance(annotation, np.ndarray) and annotation.dtype.kind in "iu" \
+            or hasattr(annotation, "data_ptr"):
+        return annotation
+    codes = np.empty(len(annotation), dtype=np.int32)
+    for i, a in enumerate(annotation):
+        if isinstance(a, (int, np.integer)) and not isinstance(a, bool):
+            codes[i] = a
+        elif a in ANNOTATIONS:
+            codes[i] = ANNOTATIONS.index(a)
+        else:
+            raise ValueError("%s: label %d has annotation %r, not one of %s"
+                             % (what, i, a, ", ".join(ANNOTATIONS)))
+    return codes
+
+
+def read_labels_bed(path):
+    """A labels.bed file as the reference's tests write it -- chrom, chromStart, chromEnd,
+    annotation, separated by white space -- as (the `labels` entry of one contig for
+    ProblemSet.label_errors: (chromStart, chromEnd, annotation codes) int32 arrays, the chrom
+    values as a list).  An unknown annotation raises ValueError naming the line."""
+    chrom, start, end, codes = [], [], [], []
+    with open(path) as f:
+        for number, line in enumerate(f, 1):
+            fields = line.split()
+            if not fields:
+                continue
+            if len(fields) != 4:
+                raise ValueError("%s: line %d does not have four columns" % (path, number))
+            if fields[3] not in ANNOTATIONS:
+                raise ValueError("%s: line %d: unknown annotation %r (one of %s)"
+                                 % (path, number, fields[3], ", ".join(ANNOTATIONS)))
+            try:
+                start.append(int(fields[1]))
+                end.append(int(fields[2]))
+            except ValueError:
+                raise ValueError("%s: line %d: chromStart and chromEnd must be integers"
+                                 % (path, number))
+            chrom.append(fields[0])
+            codes.append(ANNOTATIONS.index(fields[3]))
+    return (np.array(start, dtype=np.int32), np.array(end, dtype=np.int32),
+            np.array(codes, dtype=np.int32)), chrom
+
+
 def _extreme(v, largest):
     """the smallest or largest entry of a read array, wherever it lives"""
     return int((v.max() if largest else v.min()).item())
@@ -112,6 +161,7 @@ class ProblemSet:
         self._lib = lib or _native.lib
         self._h = ctypes.c_void_p()
         self.dense = False
+        self.device = device
         self.contigs = [(np.ascontiguousarray(c, dtype=np.int32),
                          np.ascontiguousarray(w, dtype=np.int32)) for c, w in contigs]
         self.problems = [(int(c), float(p)) for c, p in problems]
@@ -142,6 +192,7 @@ class ProblemSet:
         self._lib = lib or _native.lib
         self._h = ctypes.c_void_p()
         self.dense = True
+        self.device = device
         self.problems = [(int(c), float(p)) for c, p in problems]
         if len(contigs) == 0:
             raise ValueError("from_dense: no contig")
@@ -195,6 +246,7 @@ class ProblemSet:
         self._lib = lib or _native.lib
         self._h = ctypes.c_void_p()
         self.dense = True
+        self.device = device
         self.problems = [(int(c), float(p)) for c, p in problems]
         args, keep, ext = reads_arguments(reads, extents, bases_counted, device, "from_reads")
         self.contig_starts = [lo for lo, _ in ext]
@@ -296,6 +348,89 @@ class ProblemSet:
                                % self._lib.peakseg_hip_last_error().decode())
         return [tuple(a[offs[p]:offs[p + 1]] for a in cols) for p in range(k)]
 
+    def label_errors(self, labels, first_chromStart=None, torch_device=None):
+        """The label errors of every problem of a solved set made by from_dense or from_reads,
+        counted on the device from the resident tables (peakseg_hip_problem_set_pack_label_errors;
+        the definitions are in include/peaksegdisk_hip.h).  labels: a list over CONTIGS of
+        (chromStart, chromEnd, annotation) -- the first two 1-d contiguous int32 numpy arrays or
+        torch tensors, annotation an int32 array of codes (ANNOTATIONS) or a list of the four
+        strings --, an empty entry (or None) for a contig without labels.  Tensors on the set's
+        cuda device are read in place; one call takes one kind of memory.  first_chromStart as in
+        segment_columns().  Without torch_device: (totals, per_label) -- totals an int32 array
+        [n_problems, 5] of errors, fp, fn, possible_fp, possible_fn; per_label a list over problems
+        of (count, fp, fn) int32 arrays, one entry per label of the problem's contig in the order
+        given.  With torch_device: (rows int64 numpy[k + 1], count, fp, fn, totals) where the four
+        are tensors that alias the library's buffers: nothing is downloaded, and they are valid
+        until the next solve(), the next label_errors() or close()."""
+        k = len(self.problems)
+        n_contigs = len(self.contig_bases) if self.dense else len(self.contigs)
+        if len(labels) != n_contigs:
+            raise ValueError("label_errors: one entry per contig (%d entries, %d contigs)"
+                             % (len(labels), n_contigs))
+        first = None
+        if first_chromStart is not None:
+            first = np.ascontiguousarray(first_chromStart, dtype=np.int32)
+            if first.shape != (n_contigs,):
+                raise ValueError("first_chromStart: one value per contig")
+        names = ("chromStart", "chromEnd", "annotation")
+        keep, sides, lengths = [], [], []
+        ptrs = ([], [], [])
+        for c, entry in enumerate(labels):
+            if entry is None or len(entry) == 0:
+                lengths.append(0)
+                for q in ptrs:
+                    q.append(0)
+                continue
+            if len(entry) != 3:
+                raise ValueError("label_errors: contig %d is not (chromStart, chromEnd, annotation)"
+                                 % c)
+            entry = list(entry)
+            entry[2] = annotation_codes(entry[2], "label_errors: contig %d" % c)
+            n = None
+            for j in range(3):
+                ptr, m, side, ref = _dense_pointer(c, entry[j], self.device,
+                                                   "label_errors: contig %d " + names[j])
+                if n is not None and m != n:
+                    raise ValueError("label_errors: contig %d has %d chromStart and %d %s"
+                                     % (c, n, m, names[j]))
+                n = m
+                keep.append(ref)
+                sides.append((side, c))
+                ptrs[j].append(ptr if m else 0)
+            lengths.append(n)
+        for side, c in sides:
+            if side != sides[0][0]:
+                raise ValueError("label_errors: contig %d is in %s memory but contig %d is in %s "
+                                 "memory; one call takes one kind" % (c, side, sides[0][1], sides[0][0]))
+        rows = np.zeros(k, dtype=np.int64)
+        out = [ctypes.c_void_p() for _ in range(4)]
+        total = self._lib.peakseg_hip_problem_set_pack_label_errors(
+            self._h, first.ctypes.data if first is not None else None,
+            (ctypes.c_longlong * n_contigs)(*lengths),
+            *[(ctypes.c_void_p * n_contigs)(*q) for q in ptrs],
+            1 if sides and sides[0][0] == "device" else 0, rows.ctypes.data,
+            *[ctypes.byref(q) for q in out])
+        del keep  # (the library holds no reference to the caller's buffers after the call)
+        if total < 0:
+            err = RuntimeError("pack_label_errors: %s" % self._lib.peakseg_hip_last_error().decode())
+            err.status = int(-total) if total < -1 else _native.ERROR_DEVICE_SOLVER
+            raise err
+        total = int(total)
+        offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            cols = tuple(device_array(q.value or 0, total, np.int32, dev) for q in out[:3])
+            return (offs,) + cols + (device_array(out[3].value or 0, 5 * k, np.int32, dev).view(k, 5),)
+        cols = [np.empty(total, dtype=np.int32) for _ in range(3)]
+        totals = np.empty((k, 5), dtype=np.int32)
+        if self._lib.peakseg_hip_problem_set_packed_label_errors_download(
+                self._h, *[a.ctypes.data for a in cols], totals.ctypes.data) != 0:
+            raise RuntimeError("packed_label_errors_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        return totals, [tuple(a[offs[p]:offs[p + 1]] for a in cols) for p in range(k)]
+
     def loss(self, p):
         """The ten fields of the reference's loss.tsv row of problem p (api.col_name_list["loss"]),
         as float64."""
@@ -310,8 +445,10 @@ class ProblemSet:
         b = ctypes.c_float()
         st = self._lib.peakseg_hip_problem_set_solve(self._h, ctypes.byref(f), ctypes.byref(b))
         if st != 0:
-            raise RuntimeError("peakseg_hip_problem_set_solve: status %d: %s" % (
+            err = RuntimeError("peakseg_hip_problem_set_solve: status %d: %s" % (
                 st, self._lib.peakseg_hip_last_error().decode()))
+            err.status = st
+            raise err
         return f.value, b.value
 
     def result(self, p):

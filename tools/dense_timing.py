@@ -33,8 +33,17 @@
                 is the solve's.  For the one-contig set the legs run on its first
                 --reads-solve-bases bases (the whole contig's solve takes minutes).
 
+(l) --labels: the label errors and nothing else.  Set (b) with one penalty
+    per contig and 32 random labels per contig, and the first 2.5e7 bases of (a) at four penalties
+    with 10^4 labels, labels in cuda tensors: HIP events of peakseg_hip_problem_set_pack_label_errors
+    (zeroing, translate kernel, count kernel), warmed, --reps repetitions, minimum / median /
+    maximum, next to the segment statistics launch and the forward kernel of the same set in the
+    same run; the first problems' totals are compared with a brute-force count before any time is
+    printed.  Then the target-interval search of Mono27ac with its golden labels at widths 1, 4 and
+    8: rounds, models and seconds.
+
 usage: python tools/dense_timing.py [--contigs 6144] [--reps 20] [--e2e-reps 2] [--skip-long]
-       [--skip-e2e] [--skip-stats] [--reads [--reads-bins 10000000] [--reads-solve-bases 2500000]]
+       [--skip-e2e] [--skip-stats] [--labels] [--reads [--reads-bins 10000000] [--reads-solve-bases 2500000]]
 One JSON line per part on stdout."""
 import argparse
 import ctypes
@@ -63,6 +72,7 @@ ap.add_argument("--skip-long", action="store_true")
 ap.add_argument("--skip-e2e", action="store_true")
 ap.add_argument("--skip-stats", action="store_true")
 ap.add_argument("--reads", action="store_true")
+ap.add_argument("--labels", action="store_true")
 ap.add_argument("--reads-bins", type=int, default=10 ** 7)
 ap.add_argument("--reads-solve-bases", type=int, default=2500000)
 args = ap.parse_args()
@@ -259,8 +269,104 @@ def reads_mode():
             reads_legs("r_legs_many_contigs_" + order, sets[order], extents, problems_, args.e2e_reps)
 
 
+def brute_totals(columns, labels):
+    """[errors, fp, fn] of one model by looking at every (peak, label) pair"""
+    ps, pe = columns[0][1::2].astype(np.int64), columns[1][1::2].astype(np.int64)
+    fp = fn = 0
+    for ls, le, a in zip(*[x.tolist() for x in labels]):
+        over = int(np.sum((ps < le) & (ls < pe)))
+        n = over if a in (0, 3) else int(np.sum((ls <= ps) & (ps < le))) if a == 1 else \
+            int(np.sum((ls < pe) & (pe <= le)))
+        fp += int(a != 3 and n >= (1 if a == 0 else 2))
+        fn += int(a != 0 and n == 0)
+    return [fp + fn, fp, fn]
+
+
+def labels_laps(part, tensors_, problems_, labels_host, reps):
+    """one JSON line: the label errors, the statistics launch and the forward kernel of one set"""
+    labels_dev = [tuple(torch.from_numpy(a).to("cuda:0") for a in e) for e in labels_host]
+    s = ProblemSet.from_dense(tensors_, problems_)
+    try:
+        forward_ms = s.solve()[0]
+        k = len(problems_)
+        ptr = [ctypes.c_void_p() for _ in range(4)]
+        stats = []
+        for rep in range(reps + 3):
+            assert lib.peakseg_hip_problem_set_pack_segment_stats(
+                s._h, None, None, *[ctypes.byref(q) for q in ptr]) >= 0, _native.last_error()
+            ms = ctypes.c_float()
+            lib.peakseg_hip_segment_stats_last_ms(ctypes.byref(ms))
+            if rep >= 3:  # warmed
+                stats.append(ms.value)
+        laps = []
+        for rep in range(reps + 3):
+            offs = s.label_errors(labels_dev, torch_device="cuda:0")[0]
+            ms = ctypes.c_float()
+            lib.peakseg_hip_label_errors_last_ms(ctypes.byref(ms))
+            if rep >= 3:
+                laps.append(ms.value)
+        totals, _ = s.label_errors(labels_dev)
+        columns = s.segment_columns()
+        for p in range(min(k, 4)):
+            assert totals[p][:3].tolist() == brute_totals(columns[p], labels_host[problems_[p][0]]), p
+        segments = sum(len(c[0]) for c in columns)
+        build = s.kernel_build
+    finally:
+        s.close()
+    med = statistics.median(laps)
+    print(json.dumps({
+        "part": part, "problems": k, "labels": int(sum(len(e[0]) for e in labels_host)),
+        "label_rows": int(offs[-1]), "segments": segments, "reps": reps, "label_errors_ms": mmm(laps),
+        "segment_stats_ms": mmm(stats), "forward_kernel_ms": forward_ms, "kernel_build": build,
+        "label_errors_share_of_forward": med / forward_ms if forward_ms > 0 else None,
+        "label_errors_over_segment_stats": med / statistics.median(stats)}), flush=True)
+
+
+def labels_mode():
+    rng = np.random.default_rng(1)
+
+    def random_labels(n, bases):
+        ls = rng.integers(0, bases, n)
+        return (ls.astype(np.int32), (ls + rng.integers(1, 5001, n)).astype(np.int32),
+                rng.integers(0, 4, n).astype(np.int32))
+    grid_ = synthetic.penalty_grid()
+    tensors_ = []
+    for k in range(args.contigs):
+        cs, ce, cnt = synthetic.poisson_coverage(10000, seed=k)
+        tensors_.append(expand(cnt, (ce - cs).astype(np.int64)))
+    labels_laps("l_b_many_contigs_one_penalty_each_32_labels", tensors_,
+                [(k, float(grid_[k % 64])) for k in range(args.contigs)],
+                [random_labels(32, len(t)) for t in tensors_], args.reps)
+    del tensors_
+    torch.cuda.empty_cache()
+    if not args.skip_long:
+        cs, ce, cnt = synthetic.poisson_coverage(10 ** 6, seed=1)
+        long_t = expand(cnt, (ce - cs).astype(np.int64))[:25 * 10 ** 6]
+        labels_laps("l_a_first_2.5e7_bases_4_penalties_1e4_labels", [long_t],
+                    [(0, 0.72), (0, 37.3), (0, 1550.5), (0, 51795.0)],
+                    [random_labels(10 ** 4, len(long_t))], args.reps)
+        del long_t
+        torch.cuda.empty_cache()
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    cols = np.loadtxt(os.path.join(golden, "Mono27ac.bedGraph"), usecols=(1, 2, 3), dtype=np.int64)
+    dense = np.repeat(cols[:, 2], cols[:, 1] - cols[:, 0]).astype(np.int32)
+    mono_labels, _ = psd.read_labels_bed(os.path.join(golden, "Mono27ac.labels.bed"))
+    psd.targetInterval_dense(dense, mono_labels, width=8, chrom_starts=[int(cols[0, 0])])  # warms
+    for width in (1, 4, 8):
+        t0 = time.time()
+        res = psd.targetInterval_dense(dense, mono_labels, width=width, chrom_starts=[int(cols[0, 0])])
+        print(json.dumps({"part": "l_target_interval_mono27ac", "width": width, "rounds": res.rounds,
+                          "models": len(res.models), "seconds": time.time() - t0,
+                          "min_log_lambda": res.min_log_lambda, "max_log_lambda": res.max_log_lambda,
+                          "exact": [res.lower_exact, res.upper_exact],
+                          "min_errors": res.min_errors}), flush=True)
+
+
 if args.reads:
     reads_mode()
+    sys.exit(0)
+if args.labels:
+    labels_mode()
     sys.exit(0)
 
 
