@@ -47,6 +47,11 @@ extern "C" {
                                       or an annotation code outside 0..3; the contig, the label's
                                       index and the reason are in peakseg_hip_last_error() */
 
+#define ERROR_FEATURE_ARGUMENTS 20 /* coverage statistics that cannot be computed: a negative number
+                                      of ranks or more than peakseg_hip_coverage_stats_max_ranks, a
+                                      rank outside 0 .. bases - 1 of its contig; the contig and the
+                                      rank are in peakseg_hip_last_error() */
+
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
  *                               per GPU sets it from its rank
@@ -452,6 +457,45 @@ int peakseg_hip_problem_set_packed_label_errors_download(psd_problem_set *set, i
                                                          int *fp_out, int *fn_out, int *totals_out);
 /* milliseconds (HIP events) of the calling thread's last pack_label_errors: zeroing and launches */
 int peakseg_hip_label_errors_last_ms(float *ms);
+
+/* Order statistics and moments of the per-base coverage of every contig of a set made from dense
+ * counts or reads, computed on the device from the resident runs: the inputs of a penalty-learning
+ * regression (quartiles, mean, sd, bases, runs).  A contig's runs (count_i, weight_i), i < R, stand
+ * for the vector x that repeats count_i weight_i times; B = sum of weight_i < 2^31 is its bases.
+ *   order statistic  for a 0-based rank r in [0, B): x_(r) is the smallest v with
+ *                    sum over count_i <= v of weight_i  >  r, which is sort(x)[r]
+ *   moments          six words per contig: bases B, runs R, S1 = sum weight_i count_i, and
+ *                    S2 = sum weight_i count_i^2 (up to 2^84) as three sums that each stay below
+ *                    2^63: with count = ch 2^16 + cl,  Q0 = sum w cl^2, Q1 = sum w cl ch,
+ *                    Q2 = sum w ch^2, and S2 = Q0 + 2^17 Q1 + 2^32 Q2
+ * n_ranks: ranks per contig, 0 (moments only) to peakseg_hip_coverage_stats_max_ranks(); ranks:
+ * host array, contig c's ranks are ranks[c * n_ranks ...], in any order, repeats allowed.  value
+ * (int32, n_contigs * n_ranks) receives the order statistics in the order of the ranks, moments
+ * (n_contigs * 6) the words {bases, runs, S1, Q0, Q1, Q2}.  Integer arithmetic only: the same
+ * whatever the schedule, and exact for every count in [0, 2^31) and every weight.  The set may be
+ * solved or not, and the call leaves what a solve made (the segment tables, the packed columns)
+ * as it is.  The number of launches does not depend on the number of contigs: one for the
+ * moments and two per 8-bit digit up to the highest one that is not zero in the whole set (counts
+ * below 256: one digit pass; full-range counts: four).
+ * Returns n_contigs * n_ranks; -1 for a set that was not made from dense counts or reads;
+ * -ERROR_FEATURE_ARGUMENTS for n_ranks < 0 or above the maximum and for a rank outside [0, bases)
+ * of its contig, which the host checks before anything is launched; the text is in
+ * peakseg_hip_last_error.  The device addresses stay valid until this function is called again or
+ * the set is destroyed; ..._download copies value and moments (either may be NULL) to host arrays
+ * and returns -1 when there is nothing packed. */
+long long peakseg_hip_problem_set_pack_coverage_stats(psd_problem_set *set, int n_ranks,
+                                                      const long long *ranks, const int **value_dev,
+                                                      const unsigned long long **moments_dev);
+int peakseg_hip_problem_set_packed_coverage_stats_download(psd_problem_set *set, int *value_out,
+                                                           unsigned long long *moments_out);
+/* the tile of those launches: runs one workgroup reads (tests aim at its boundaries) */
+int peakseg_hip_coverage_stats_tile_runs(void);
+/* the largest n_ranks of one call (at least 10) */
+int peakseg_hip_coverage_stats_max_ranks(void);
+/* milliseconds (HIP events) of the calling thread's last pack_coverage_stats: zeroing and launches */
+int peakseg_hip_coverage_stats_last_ms(float *ms);
+/* the digit passes the calling thread's last pack_coverage_stats launched (0: moments only) */
+int peakseg_hip_coverage_stats_last_passes(int *digit_passes);
 
 /* Where a round of the parallel penalty search looks besides its secant penalty: up to `extras`
  * penalties between over_penalty (the bracket's smaller penalty, 0 allowed) and under_penalty (its

@@ -10,9 +10,10 @@ from .api import (PeakSegError, PeakSegFPOP_dir, PeakSegFPOP_df, PeakSegFPOP_fil
                   PeakSegFPOP_dir_batch, col_name_list, paste,
                   sequentialSearch_dir, sequentialSearch_dir_batch, parallelSearch_dir,
                   parallelSearch_dir_batch, writeBedGraph, targetInterval_dense,
-                  targetInterval_reads)
+                  targetInterval_reads, problem_features_dense, problem_features_reads,
+                  predict_penalties)
 from ._native import last_fanout  # noqa: F401
-from .grid import ProblemSet, read_labels_bed  # noqa: F401
+from .grid import ProblemSet, read_labels_bed, features_from_stats  # noqa: F401
 
 __all__ = ["PeakSegFPOP_file", "PeakSegFPOP_dir", "PeakSegFPOP_df", "PeakSegFPOP_vec",
            "PeakSegFPOP_dense", "PeakSegFPOP_reads", "coverage_from_reads",
@@ -20,5 +21,6 @@ __all__ = ["PeakSegFPOP_file", "PeakSegFPOP_dir", "PeakSegFPOP_df", "PeakSegFPOP
            "parallelSearch_dir", "parallelSearch_dir_batch",
            "writeBedGraph", "col_name_list", "paste",
            "ProblemSet", "last_fanout", "read_labels_bed", "targetInterval_dense",
-           "targetInterval_reads",
+           "targetInterval_reads", "problem_features_dense", "problem_features_reads",
+           "predict_penalties", "features_from_stats",
            "PeakSegError"]

@@ -16,6 +16,7 @@ ERROR_DEVICE_MEMORY = 14
 ERROR_DENSE_ARGUMENTS = 17
 ERROR_READS_ARGUMENTS = 18
 ERROR_LABEL_ARGUMENTS = 19
+ERROR_FEATURE_ARGUMENTS = 20
 
 
 class PsdResult(ctypes.Structure):
@@ -215,6 +216,20 @@ def declare(lib):
     lib.peakseg_hip_problem_set_packed_label_errors_download.restype = c.c_int
     lib.peakseg_hip_label_errors_last_ms.argtypes = [c.POINTER(c.c_float)]
     lib.peakseg_hip_label_errors_last_ms.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_coverage_stats.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_pack_coverage_stats.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_coverage_stats_download.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_problem_set_packed_coverage_stats_download.restype = c.c_int
+    lib.peakseg_hip_coverage_stats_tile_runs.argtypes = []
+    lib.peakseg_hip_coverage_stats_tile_runs.restype = c.c_int
+    lib.peakseg_hip_coverage_stats_max_ranks.argtypes = []
+    lib.peakseg_hip_coverage_stats_max_ranks.restype = c.c_int
+    lib.peakseg_hip_coverage_stats_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_coverage_stats_last_ms.restype = c.c_int
+    lib.peakseg_hip_coverage_stats_last_passes.argtypes = [c.POINTER(c.c_int)]
+    lib.peakseg_hip_coverage_stats_last_passes.restype = c.c_int
     lib.peakseg_hip_search_place_penalties.argtypes = [
         c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
     lib.peakseg_hip_search_place_penalties.restype = c.c_int
@@ -252,6 +267,10 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_pack_label_errors",
     "peakseg_hip_problem_set_packed_label_errors_download",
     "peakseg_hip_label_errors_last_ms", "peakseg_hip_search_place_penalties",
+    "peakseg_hip_problem_set_pack_coverage_stats",
+    "peakseg_hip_problem_set_packed_coverage_stats_download",
+    "peakseg_hip_coverage_stats_tile_runs", "peakseg_hip_coverage_stats_max_ranks",
+    "peakseg_hip_coverage_stats_last_ms", "peakseg_hip_coverage_stats_last_passes",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -397,10 +397,12 @@ def _label_frame(chrom, entry, columns):
 LABEL_TOTALS = ["errors", "fp", "fn", "possible.fp", "possible.fn"]
 
 
-def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None):
+def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, penalty_model=None):
     """What PeakSegFPOP_dense and PeakSegFPOP_reads share: the problems of `pens` (one list per
     contig), the set -- make_set(problems) -> (ProblemSet, chromStart of each contig's first
-    base) --, its solution, and the reference's data frames, nested as `pens` is."""
+    base) --, its solution, and the reference's data frames, nested as `pens` is.
+    penalty_model: `pens` holds one placeholder (Inf) per contig; every problem gets the penalty
+    the model predicts from the set's coverage features before the one solve."""
     if labels is not None:
         labels = _label_lists(labels, len(pens), single, "contig")
     problems, pen_strs = [], []
@@ -419,6 +421,14 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None):
         detail = _native.last_error()
         raise PeakSegError(status, "%s (%s)" % (msg, detail) if detail else msg)
     try:
+        features = None
+        if penalty_model is not None:
+            features = pset.coverage_features()
+            for p, pen_num in enumerate(predict_penalties(features, penalty_model).tolist()):
+                _check_pen_num(pen_num)
+                pen_strs[p] = paste(pen_num)
+                problems[p] = (problems[p][0], float(pen_strs[p]))
+                pset.set_penalty(p, problems[p][1])
         try:
             pset.solve()
         except RuntimeError as e:
@@ -462,6 +472,8 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None):
             flat[-1].label_errors = _label_frame(chrom, labels[c], label_cols[p])
             for name, value in zip(LABEL_TOTALS, label_totals[p].tolist()):
                 flat[-1].loss[name] = value
+        if features is not None:
+            flat[-1].features = features.iloc[c]
     out, o = [], 0
     for q in pens:
         out.append(flat[o:o + len(q)])
@@ -469,8 +481,19 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None):
     return out[0] if single else out
 
 
-def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=None, device=0,
-                      stats=False, labels=None):
+def _penalty_source(penalties, penalty_model, n_contigs, noun):
+    """the `pens` of _solve_dense_set from exactly one of penalties / penalty_model, checked before
+    any device work"""
+    if (penalties is None) == (penalty_model is None):
+        raise ValueError("exactly one of penalties and penalty_model must be given")
+    if penalty_model is None:
+        return _penalty_lists(penalties, n_contigs, noun)
+    _check_penalty_model(penalty_model)
+    return [[float("inf")] for _ in range(n_contigs)]
+
+
+def PeakSegFPOP_dense(count_vecs, penalties=None, chrom="chrUnknown", chrom_starts=None, device=0,
+                      stats=False, labels=None, penalty_model=None):
     """PeakSegFPOP_vec without its files: dense integer coverage (one count per base) is
     run-length encoded and solved on the GPU, and the reference's result comes back as data
     frames.  count_vecs: one vector or a list of them (int32 numpy arrays or torch tensors are
@@ -489,14 +512,21 @@ def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=No
     vector without labels: every result also gets .label_errors, a data frame chrom, chromStart,
     chromEnd, annotation, count, fp, fn, status (correct / false positive / false negative) with
     one row per label, counted on the GPU (ProblemSet.label_errors), and $loss the columns errors,
-    fp, fn, possible.fp and possible.fn."""
+    fp, fn, possible.fp and possible.fn.
+    penalty_model instead of penalties: {"intercept": float, "weights": {feature name: float}}, a
+    fitted log(penalty) = intercept + sum of weight x feature.  The set is made with one problem
+    per vector, its coverage features are computed on the GPU (ProblemSet.coverage_features), each
+    problem gets its predicted penalty (predict_penalties), and one solve follows: each vector
+    yields a list of one result -- what `penalties` [[p]] gives for that penalty -- which also
+    carries .features, the vector's row of the feature table.  Exactly one of penalties and
+    penalty_model must be given (ValueError)."""
     from .grid import ProblemSet
     single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
         len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
     vecs = [count_vecs] if single else list(count_vecs)
     if len(vecs) == 0:
         raise ValueError("count.vecs must hold at least one vector")
-    pens = _penalty_lists(penalties, len(vecs), "vector")
+    pens = _penalty_source(penalties, penalty_model, len(vecs), "vector")
     contigs = [_int32_vector(v) for v in vecs]
     if chrom_starts is None:
         chrom_starts = [0] * len(vecs)
@@ -504,7 +534,7 @@ def PeakSegFPOP_dense(count_vecs, penalties, chrom="chrUnknown", chrom_starts=No
         raise ValueError("chrom.starts: one per vector")
     return _solve_dense_set(
         lambda problems: (ProblemSet.from_dense(contigs, problems, device=device), chrom_starts),
-        pens, chrom, stats, single, "<dense counts>", labels)
+        pens, chrom, stats, single, "<dense counts>", labels, penalty_model)
 
 
 # ---- aligned reads in memory (additive: the pile-up happens on the GPU) -----------------------
@@ -519,8 +549,8 @@ def _read_contigs(reads):
     return single, [reads] if single else list(reads)
 
 
-def PeakSegFPOP_reads(reads, penalties, chrom="chrUnknown", extents=None, bases_counted="each",
-                      device=0, stats=False, labels=None):
+def PeakSegFPOP_reads(reads, penalties=None, chrom="chrUnknown", extents=None, bases_counted="each",
+                      device=0, stats=False, labels=None, penalty_model=None):
     """PeakSegFPOP_dense with the step in front of it: aligned reads are piled up into coverage,
     run-length encoded and solved on the GPU.  reads: one contig -- (chromStart, chromEnd) or
     (chromStart, chromEnd, count), one entry per read, in any order -- or a list of contigs
@@ -529,7 +559,8 @@ def PeakSegFPOP_reads(reads, penalties, chrom="chrUnknown", extents=None, bases_
     per contig; extents: per contig (a single pair for a single contig) the (chromStart, chromEnd)
     whose bases are the data, default (min chromStart, max chromEnd) of its reads;
     bases_counted: "each" base of a read or only its "end".  Coordinates are genomic: base 0 of a
-    contig is its extent's chromStart.  Results, `stats` and `labels` as PeakSegFPOP_dense."""
+    contig is its extent's chromStart.  Results, `stats`, `labels` and `penalty_model` as
+    PeakSegFPOP_dense."""
     from .grid import ProblemSet
     single, contigs = _read_contigs(reads)
     names = ("chromStart", "chromEnd", "count")
@@ -537,13 +568,104 @@ def PeakSegFPOP_reads(reads, penalties, chrom="chrUnknown", extents=None, bases_
                if isinstance(entry, (tuple, list)) else entry for entry in contigs]
     if single and extents is not None:
         extents = [extents]
-    pens = _penalty_lists(penalties, len(contigs), "contig")
+    pens = _penalty_source(penalties, penalty_model, len(contigs), "contig")
 
     def make_set(problems):
         pset = ProblemSet.from_reads(contigs, problems, extents=extents,
                                      bases_counted=bases_counted, device=device)
         return pset, pset.contig_starts
-    return _solve_dense_set(make_set, pens, chrom, stats, single, "<aligned reads>", labels)
+    return _solve_dense_set(make_set, pens, chrom, stats, single, "<aligned reads>", labels,
+                            penalty_model)
+
+
+# ---- coverage features and learned penalties (additive) ----------------
+
+def _check_penalty_model(model):
+    """{"intercept": float, "weights": {feature name: float}} or ValueError -> (intercept, weights)"""
+    from .grid import FEATURE_NAMES
+    if not isinstance(model, dict) or set(model) != {"intercept", "weights"} or \
+            not isinstance(model["weights"], dict):
+        raise ValueError('penalty_model: {"intercept": float, "weights": {feature name: float}}')
+    for name in model["weights"]:
+        if name not in FEATURE_NAMES:
+            raise ValueError("penalty_model: unknown feature %r" % (name,))
+    return float(model["intercept"]), {n: float(w) for n, w in model["weights"].items()}
+
+
+def predict_penalties(features, model):
+    """The penalties a fitted model predicts: features: the data frame of coverage_features /
+    problem_features_* (one row per contig); model: {"intercept": float, "weights": {feature name:
+    float}}, log(penalty) = intercept + the sum of weight x feature.  Returns a float64 array, one
+    penalty per row: exp of the prediction, passed through paste() as every penalty is (15
+    significant digits).  ValueError for an unknown feature name, and for a feature with a non-zero
+    weight that is not finite for some contig (it names the contig and the feature): a NaN
+    never becomes a penalty."""
+    intercept, weights = _check_penalty_model(model)
+    log_penalty = np.full(len(features), intercept, dtype=np.float64)
+    for name, weight in weights.items():
+        if weight == 0.0:
+            continue
+        column = features[name].to_numpy(dtype=np.float64)
+        bad = np.flatnonzero(~np.isfinite(column))
+        if len(bad):
+            raise ValueError("predict_penalties: contig %d: feature %r is %r, and its weight is not zero"
+                             % (int(bad[0]), name, float(column[bad[0]])))
+        log_penalty += weight * column
+    if not np.all(np.isfinite(log_penalty)):
+        bad = int(np.flatnonzero(~np.isfinite(log_penalty))[0])
+        raise ValueError("predict_penalties: contig %d: the predicted log(penalty) is %r"
+                         % (bad, float(log_penalty[bad])))
+    with np.errstate(over="ignore"):
+        return np.array([float(paste(float(p))) for p in np.exp(log_penalty)], dtype=np.float64)
+
+
+def _feature_frame(make_set, n_contigs, label):
+    """the coverage features of a set made for them alone: a problem per contig at penalty Inf (the
+    closed form: never launched)"""
+    try:
+        pset = make_set([(c, float("inf")) for c in range(n_contigs)])[0]
+    except RuntimeError as e:
+        status = getattr(e, "status", _native.ERROR_DEVICE_SOLVER)
+        msg = _native.status_message(status, label, "", "")
+        detail = _native.last_error()
+        raise PeakSegError(status, "%s (%s)" % (msg, detail) if detail else msg)
+    try:
+        return pset.coverage_features()
+    finally:
+        pset.close()
+
+
+def problem_features_dense(count_vecs, device=0):
+    """The feature table of dense coverage: count_vecs as PeakSegFPOP_dense; a pandas data frame
+    with one row per vector and the 36 columns of ProblemSet.coverage_features -- quartiles, mean,
+    sd, bases and data (runs), each also under log+1, log and log.log --, computed on the GPU from
+    the runs the encoder leaves there."""
+    from .grid import ProblemSet
+    single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
+        len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
+    vecs = [count_vecs] if single else list(count_vecs)
+    if len(vecs) == 0:
+        raise ValueError("count.vecs must hold at least one vector")
+    contigs = [_int32_vector(v) for v in vecs]
+    return _feature_frame(
+        lambda problems: (ProblemSet.from_dense(contigs, problems, device=device), None),
+        len(contigs), "<dense counts>")
+
+
+def problem_features_reads(reads, extents=None, bases_counted="each", device=0):
+    """problem_features_dense with the pile-up in front of it: reads, extents and bases_counted as
+    PeakSegFPOP_reads."""
+    from .grid import ProblemSet
+    single, contigs = _read_contigs(reads)
+    names = ("chromStart", "chromEnd", "count")
+    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
+               if isinstance(entry, (tuple, list)) else entry for entry in contigs]
+    if single and extents is not None:
+        extents = [extents]
+    return _feature_frame(
+        lambda problems: (ProblemSet.from_reads(contigs, problems, extents=extents,
+                                                bases_counted=bases_counted, device=device), None),
+        len(contigs), "<aligned reads>")
 
 
 # ---- the target interval of labelled contigs (additive; DESIGN.md section 12) ---------------

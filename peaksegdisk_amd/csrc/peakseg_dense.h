@@ -322,6 +322,7 @@ int dense_create_encoded(int device, int n_contigs, const long long *contig_n_ba
     s->contig_bases.push_back(contig_n_bases[c]);
     s->contig_sum.push_back(cs.sum);
     s->contig_constant.push_back(cs.mn == cs.mx);
+    s->contig_max.push_back(cs.mx);
     /* psd_log is strictly increasing on the integers: the logs of the integer extremes are the
      * extremes of the logs (drv:198-204) */
     min_lm[(size_t)c] = psd_log((double)cs.mn);

@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, reads, labels, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -84,6 +84,8 @@
 #include "reads_pileup.h"
 /* label errors of every model from the resident tables */
 #include "label_errors.h"
+/* order statistics and moments of every contig's coverage from the resident runs */
+#include "coverage_stats.h"
 
 #include <ctype.h>
 #include <errno.h>
@@ -120,6 +122,7 @@
 #include "peakseg_dense.h"
 #include "peakseg_reads.h"
 #include "peakseg_labels.h"
+#include "peakseg_features.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -168,6 +171,8 @@ extern "C" void peakseg_hip_problem_set_destroy(psd_problem_set *s) {
   for (auto &e : s->stats.ev)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : s->labels.ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto &e : s->features.ev)
     if (e) (void)hipEventDestroy(e);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   if (s->stream2) (void)hipStreamDestroy(s->stream2);
@@ -481,6 +486,10 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
                 "error code %d: labels that cannot be counted (a negative number of labels, a NULL or "
                 "misaligned array, a label with chromStart >= chromEnd or an annotation code outside "
                 "0..3)", status);
+    PSD_MESSAGE(ERROR_FEATURE_ARGUMENTS,
+                "error code %d: coverage statistics that cannot be computed (a negative number of "
+                "ranks or more than peakseg_hip_coverage_stats_max_ranks, or a rank outside "
+                "0 .. bases - 1 of its contig)", status);
     default:
       snprintf(buf, buf_len, "error code %d", status);
       break;

@@ -65,6 +65,22 @@ struct LabelTable {
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
+/* What peakseg_hip_problem_set_pack_coverage_stats keeps (peakseg_features.h): the tiles over the
+ * contigs and their descriptors (the set's geometry: made by the first call, kept), the moments,
+ * and the state of the selection, which grows to what the largest call so far needed. */
+struct FeatureTable {
+  long long *d_desc = nullptr;       /* psd::cover::DESC per contig */
+  int *d_tile_contig = nullptr;
+  long long n_tiles = -1;            /* (-1: no geometry yet) */
+  unsigned long long *moments = nullptr; /* psd::cover::MOMENTS per contig */
+  int *prefix = nullptr, *leader = nullptr, *value = nullptr; /* per contig and rank */
+  long long *resid = nullptr;
+  unsigned long long *hist = nullptr; /* psd::cover::BINS per contig and rank */
+  long long rank_capacity = 0;       /* contigs x ranks the state has room for */
+  long long total = -1;              /* entries of value[] after the last call (-1: none) */
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
 struct psd_problem_set {
   /* geometry: the contigs, the problems and where their tables start */
   int device = 0;
@@ -128,6 +144,7 @@ struct psd_problem_set {
   PackedTable pack, segs;
   StatsTable stats; /* (sets made from dense counts) */
   LabelTable labels; /* (sets made from dense counts) */
+  FeatureTable features; /* (sets made from dense counts) */
 
   /* Sets made from dense counts (peakseg_hip_problem_set_create_dense): run_end[] next to count[]
    * and weight[], the sum of each contig's counts, and which contigs are constant.  Their trivial
@@ -136,6 +153,7 @@ struct psd_problem_set {
   int *d_run_end = nullptr;
   std::vector<long long> contig_sum;
   std::vector<char> contig_constant;
+  std::vector<int> contig_max; /* each contig's largest count */
   int *d_order_run = nullptr; /* launch order of a solve that leaves trivial problems out */
 
   SolveRun run; /* per-solve state */

@@ -191,6 +191,16 @@ PSD_D void atomic_max_u64(unsigned long long *p, unsigned long long v) {
 }
 #endif
 
+/* an add to a word in LDS that other lanes and waves of the workgroup add to as well; nothing is
+ * returned (ds_add_u32) */
+#ifdef PSD_EMU
+PSD_D void lds_add_u32(unsigned *p, unsigned v) { *p += v; } /* (a block's fibers never run concurrently) */
+#else
+PSD_D void lds_add_u32(unsigned *p, unsigned v) {
+  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+#endif
+
 template <class T>
 PSD_D T *uniform_p(T *p) {
 #ifdef PSD_EMU

@@ -154,6 +154,45 @@ def reads_arguments(reads, extents, bases_counted, device, who):
     return args, keep, out_extents
 
 
+BASE_FEATURES = ("quartile.0%", "quartile.25%", "quartile.50%", "quartile.75%", "quartile.100%",
+                 "mean", "sd", "bases", "data")
+FEATURE_PREFIXES = ("", "log+1.", "log.", "log.log.")
+FEATURE_NAMES = tuple(prefix + name for prefix in FEATURE_PREFIXES for name in BASE_FEATURES)
+MOMENT_WORDS = 6    # bases, runs, S1, Q0, Q1, Q2 of peakseg_hip_problem_set_pack_coverage_stats
+
+
+def quartile_ranks(bases):
+    """(lo, hi, g) of the five type-7 quartiles of a vector of `bases` entries, from integer
+    arithmetic: h = (bases - 1) k / 4, lo = floor(h), hi = min(lo + 1, bases - 1), g = h - lo"""
+    h4 = [(bases - 1) * k for k in range(5)]
+    lo = [h // 4 for h in h4]
+    return lo, [min(r + 1, bases - 1) for r in lo], [(h % 4) / 4.0 for h in h4]
+
+
+def features_from_stats(quartile_lo, quartile_hi, bases, runs, s1, s2):
+    """The 36 features (FEATURE_NAMES) of one contig's per-base coverage x from integers, on the
+    host: quartile_lo[k], quartile_hi[k]: the order statistics x_(lo), x_(hi) of quartile_ranks(bases);
+    bases: len(x); runs: the runs of its run-length encoding; s1 = sum(x); s2 = sum(x ** 2).  The
+    quartiles are type 7 (R's default, numpy's "linear"), exact in float64; mean = s1 / bases and
+    sd = sqrt((bases s2 - s1^2) / (bases (bases - 1))) are formed from exact quotients of Python
+    integers, rounded once (sd is NaN for one base).  Then the nine under log(v + 1), log(v) and
+    log(log(v)), as numpy computes them with its warnings silenced: what is undefined is -inf or NaN
+    and stays in the vector."""
+    import math
+    from fractions import Fraction
+    bases, runs, s1, s2 = int(bases), int(runs), int(s1), int(s2)
+    g = quartile_ranks(bases)[2]
+    base = [float(int(a)) + (float(int(b)) - float(int(a))) * gk
+            for a, b, gk in zip(quartile_lo, quartile_hi, g)]
+    base.append(float(Fraction(s1, bases)))
+    base.append(math.sqrt(float(Fraction(bases * s2 - s1 * s1, bases * (bases - 1))))
+                if bases > 1 else float("nan"))
+    base += [float(bases), float(runs)]
+    base = np.array(base, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return np.concatenate([base, np.log(base + 1.0), np.log(base), np.log(np.log(base))])
+
+
 class ProblemSet:
     """contigs: list of (count, weight) int32 arrays; problems: list of (contig_index, penalty)."""
 
@@ -430,6 +469,135 @@ class ProblemSet:
             raise RuntimeError("packed_label_errors_download: %s"
                                % self._lib.peakseg_hip_last_error().decode())
         return totals, [tuple(a[offs[p]:offs[p + 1]] for a in cols) for p in range(k)]
+
+    def _coverage_stats(self, ranks, torch_device=None):
+        """one peakseg_hip_problem_set_pack_coverage_stats: ranks int64 [n_contigs, k], k at most
+        max_ranks -> (value int32 [n_contigs, k], moments uint64 [n_contigs, 6]); with torch_device
+        the value is a tensor that aliases the library's buffer"""
+        nc, k = ranks.shape
+        value_dev, moments_dev = ctypes.c_void_p(), ctypes.c_void_p()
+        total = self._lib.peakseg_hip_problem_set_pack_coverage_stats(
+            self._h, k, ranks.ctypes.data if k else None, ctypes.byref(value_dev),
+            ctypes.byref(moments_dev))
+        if total < 0:
+            err = RuntimeError("pack_coverage_stats: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+            err.status = int(-total) if total < -1 else _native.ERROR_DEVICE_SOLVER
+            raise err
+        moments = np.empty((nc, MOMENT_WORDS), dtype=np.uint64)
+        value = np.empty((nc, k), dtype=np.int32)
+        on_device = torch_device is not None
+        if self._lib.peakseg_hip_problem_set_packed_coverage_stats_download(
+                self._h, None if on_device or not k else value.ctypes.data,
+                moments.ctypes.data) != 0:
+            raise RuntimeError("packed_coverage_stats_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        if on_device:
+            import torch
+            from .parallel import device_array
+            value = device_array(value_dev.value or 0, nc * k, np.int32,
+                                 torch.device(torch_device)).view(nc, k)
+        return value, moments
+
+    def _n_contigs(self):
+        return len(self.contig_bases) if self.dense else len(self.contigs)
+
+    def coverage_order_statistics(self, ranks, torch_device=None):
+        """Order statistics of every contig's per-base coverage x (a set made by from_dense or
+        from_reads, solved or not), selected on the device from the resident runs
+        (peakseg_hip_problem_set_pack_coverage_stats): for the 0-based rank r, sort(x)[r].  ranks: an
+        integer array [n_contigs, k], or one row of k ranks for all contigs; a rank outside
+        [0, bases) of its contig raises RuntimeError with .status 20, naming the contig and the rank.
+        Returns int32 [n_contigs, k].  More ranks than the library takes in one call
+        (peakseg_hip_coverage_stats_max_ranks) make several calls.  With torch_device: a tensor on
+        that device -- of a single call it aliases the library's buffer and is valid until the next
+        coverage_* call or close(); of several calls it is their copies, joined."""
+        nc = self._n_contigs()
+        ranks = np.asarray(ranks)
+        if ranks.size and not np.issubdtype(ranks.dtype, np.integer):
+            raise ValueError("coverage_order_statistics: ranks must be integers")
+        if ranks.ndim == 1:
+            ranks = np.broadcast_to(ranks, (nc, ranks.shape[0]))
+        if ranks.ndim != 2 or ranks.shape[0] != nc:
+            raise ValueError("coverage_order_statistics: ranks: [n_contigs, k] or one row for all "
+                             "(%d contigs)" % nc)
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64)
+        most = int(self._lib.peakseg_hip_coverage_stats_max_ranks())
+        k = ranks.shape[1]
+        if k <= most:
+            return self._coverage_stats(ranks, torch_device)[0]
+        parts = []
+        for at in range(0, k, most):
+            part = self._coverage_stats(np.ascontiguousarray(ranks[:, at:at + most]), torch_device)[0]
+            parts.append(part.clone() if torch_device is not None else part)
+        if torch_device is not None:
+            import torch
+            return torch.cat(parts, dim=1)
+        return np.concatenate(parts, axis=1)
+
+    @staticmethod
+    def _moment_columns(moments):
+        s2 = np.empty(len(moments), dtype=object)
+        for c, row in enumerate(moments.tolist()):
+            s2[c] = row[3] + (row[4] << 17) + (row[5] << 32)
+        return {"bases": moments[:, 0].astype(np.int64), "runs": moments[:, 1].astype(np.int64),
+                "sum": moments[:, 2].astype(np.int64), "sum_sq": s2}
+
+    def coverage_moments(self):
+        """{"bases", "runs", "sum": int64 arrays, "sum_sq": an object array of Python ints}, one
+        entry per contig: the number of bases of its per-base coverage x, the runs of its encoding,
+        sum(x) and sum(x ** 2) (which may reach 2^84: the device carries it exactly in three 64-bit
+        words), summed on the device from the resident runs."""
+        return self._moment_columns(
+            self._coverage_stats(np.zeros((self._n_contigs(), 0), dtype=np.int64))[1])
+
+    def coverage_quantiles(self, probs=(0, .25, .5, .75, 1)):
+        """float64 [n_contigs, len(probs)]: the type-7 quantiles (R's default, numpy's "linear") of
+        every contig's per-base coverage x: with h = (len(x) - 1) p, lo = floor(h), g = h - lo,
+        x_(lo) + (x_(lo + 1) - x_(lo)) g.  For multiples of 1/4, lo and g come from integer
+        arithmetic and the result is np.quantile(x, p) bit for bit.  The order statistics are
+        selected on the device (coverage_order_statistics).  NaN or a prob outside [0, 1]: ValueError."""
+        probs = [float(p) for p in probs]
+        for p in probs:
+            if not 0.0 <= p <= 1.0:      # (NaN fails both)
+                raise ValueError("coverage_quantiles: prob %r is not in [0, 1]" % p)
+        nc = self._n_contigs()
+        lo = np.zeros((nc, len(probs)), dtype=np.int64)
+        g = np.zeros((nc, len(probs)), dtype=np.float64)
+        last = np.zeros((nc, 1), dtype=np.int64)
+        if self.dense:
+            last[:, 0] = np.asarray(self.contig_bases, dtype=np.int64) - 1
+        for j, p in enumerate(probs):
+            if (4.0 * p).is_integer():
+                h4 = last[:, 0] * int(4.0 * p)
+                lo[:, j], g[:, j] = h4 // 4, (h4 % 4) / 4.0
+            else:
+                h = last[:, 0].astype(np.float64) * p
+                lo[:, j] = np.floor(h).astype(np.int64)
+                g[:, j] = h - np.floor(h)
+        value = self.coverage_order_statistics(
+            np.concatenate([lo, np.minimum(lo + 1, last)], axis=1)).astype(np.float64)
+        a, b = value[:, :len(probs)], value[:, len(probs):]
+        return a + (b - a) * g
+
+    def coverage_features(self):
+        """The inputs of a penalty-learning regression: a pandas data frame with one row per contig
+        and the 36 columns FEATURE_NAMES -- the quartiles, mean, sd, bases and data (runs) of the
+        contig's per-base coverage, and each of them under log(v + 1), log(v) and log(log(v))
+        (features_from_stats has the definitions).  One call of the library for the order
+        statistics and the moments, from the resident runs; nothing of the coverage is downloaded."""
+        import pandas as pd
+        nc = self._n_contigs()
+        ranks = np.zeros((nc, 10), dtype=np.int64)
+        for c in range(nc if self.dense else 0):
+            lo, hi, _ = quartile_ranks(int(self.contig_bases[c]))
+            ranks[c] = lo + hi
+        value, moments = self._coverage_stats(ranks)
+        cols = self._moment_columns(moments)
+        rows = [features_from_stats(value[c, :5], value[c, 5:], cols["bases"][c], cols["runs"][c],
+                                    cols["sum"][c], cols["sum_sq"][c]) for c in range(nc)]
+        return pd.DataFrame(np.array(rows, dtype=np.float64).reshape(nc, len(FEATURE_NAMES)),
+                            columns=list(FEATURE_NAMES))
 
     def loss(self, p):
         """The ten fields of the reference's loss.tsv row of problem p (api.col_name_list["loss"]),

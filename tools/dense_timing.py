@@ -42,8 +42,17 @@
     printed.  Then the target-interval search of Mono27ac with its golden labels at widths 1, 4 and
     8: rounds, models and seconds.
 
+(f) --features: the coverage statistics and nothing else, on the two sets of
+    --labels: HIP events of peakseg_hip_problem_set_pack_coverage_stats with the ten ranks of the
+    quartiles (zeroing, the moments launch, two launches per digit pass), warmed, --reps
+    repetitions, minimum / median / maximum, next to the segment statistics launch and the forward
+    kernel of the same set in the same run, the wall time of ProblemSet.coverage_features(), and
+    the host path it replaces: the coverage downloaded, then numpy quantile + mean + std per
+    contig.  The quartiles of the two paths are compared for equality (mean and sd within 1e-9)
+    before any time is printed.
+
 usage: python tools/dense_timing.py [--contigs 6144] [--reps 20] [--e2e-reps 2] [--skip-long]
-       [--skip-e2e] [--skip-stats] [--labels] [--reads [--reads-bins 10000000] [--reads-solve-bases 2500000]]
+       [--skip-e2e] [--skip-stats] [--labels] [--features] [--reads [--reads-bins 10000000] [--reads-solve-bases 2500000]]
 One JSON line per part on stdout."""
 import argparse
 import ctypes
@@ -73,6 +82,7 @@ ap.add_argument("--skip-e2e", action="store_true")
 ap.add_argument("--skip-stats", action="store_true")
 ap.add_argument("--reads", action="store_true")
 ap.add_argument("--labels", action="store_true")
+ap.add_argument("--features", action="store_true")
 ap.add_argument("--reads-bins", type=int, default=10 ** 7)
 ap.add_argument("--reads-solve-bases", type=int, default=2500000)
 args = ap.parse_args()
@@ -362,8 +372,96 @@ def labels_mode():
                           "min_errors": res.min_errors}), flush=True)
 
 
+def features_laps(part, tensors_, problems_, reps):
+    """one JSON line: the coverage statistics, the statistics launch and the forward kernel of one
+    set, and the host path: download + numpy"""
+    from peaksegdisk_amd.grid import quartile_ranks
+    s = ProblemSet.from_dense(tensors_, problems_)
+    try:
+        forward_ms = s.solve()[0]
+        ptr = [ctypes.c_void_p() for _ in range(4)]
+        stats = []
+        for rep in range(reps + 3):
+            assert lib.peakseg_hip_problem_set_pack_segment_stats(
+                s._h, None, None, *[ctypes.byref(q) for q in ptr]) >= 0, _native.last_error()
+            ms = ctypes.c_float()
+            lib.peakseg_hip_segment_stats_last_ms(ctypes.byref(ms))
+            if rep >= 3:  # warmed
+                stats.append(ms.value)
+        ranks = np.array([sum(quartile_ranks(len(t))[:2], []) for t in tensors_], dtype=np.int64)
+        laps, walls = [], []
+        passes = ctypes.c_int()
+        for rep in range(reps + 3):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            s._coverage_stats(ranks)
+            wall = time.time() - t0
+            ms = ctypes.c_float()
+            lib.peakseg_hip_coverage_stats_last_ms(ctypes.byref(ms))
+            lib.peakseg_hip_coverage_stats_last_passes(ctypes.byref(passes))
+            if rep >= 3:
+                laps.append(ms.value)
+                walls.append(wall)
+        t0 = time.time()
+        frame = s.coverage_features()
+        frame_s = time.time() - t0
+        moments = s.coverage_moments()
+        runs = int(moments["runs"].sum())
+        build = s.kernel_build
+    finally:
+        s.close()
+    # the host path this replaces
+    torch.cuda.synchronize()
+    t0 = time.time()
+    host = [t.cpu().numpy() for t in tensors_]
+    t1 = time.time()
+    quart = np.array([np.quantile(v, [0, .25, .5, .75, 1]) for v in host])
+    mean = np.array([v.mean() for v in host])
+    sd = np.array([v.std(ddof=1) for v in host])
+    t2 = time.time()
+    names = ["quartile.0%", "quartile.25%", "quartile.50%", "quartile.75%", "quartile.100%"]
+    assert np.array_equal(frame[names].to_numpy(), quart), part
+    assert np.allclose(frame["mean"].to_numpy(), mean, rtol=1e-9, atol=0), part
+    assert np.allclose(frame["sd"].to_numpy(), sd, rtol=1e-9, atol=0), part
+    assert frame["bases"].tolist() == [float(len(v)) for v in host], part
+    med = statistics.median(laps)
+    model = 8.0 * runs * (1 + passes.value)
+    print(json.dumps({
+        "part": part, "contigs": len(tensors_), "problems": len(problems_), "runs": runs,
+        "bases": int(sum(len(v) for v in host)), "ranks_per_contig": 10,
+        "digit_passes": passes.value, "reps": reps, "results_equal": True,
+        "coverage_stats_ms": mmm(laps), "coverage_stats_call_wall_ms": mmm([w * 1e3 for w in walls]),
+        "coverage_features_call_s": frame_s,
+        "segment_stats_ms": mmm(stats), "forward_kernel_ms": forward_ms, "kernel_build": build,
+        "bytes_8R_per_reading_launch": model, "bytes_per_s_median": model / (med * 1e-3),
+        "coverage_stats_over_segment_stats": med / statistics.median(stats),
+        "coverage_stats_share_of_forward": med / forward_ms if forward_ms > 0 else None,
+        "host_download_s": t1 - t0, "host_numpy_s": t2 - t1,
+        "host_path_over_coverage_features_call": (t2 - t0) / frame_s}), flush=True)
+
+
+def features_mode():
+    grid_ = synthetic.penalty_grid()
+    tensors_ = []
+    for k in range(args.contigs):
+        cs, ce, cnt = synthetic.poisson_coverage(10000, seed=k)
+        tensors_.append(expand(cnt, (ce - cs).astype(np.int64)))
+    features_laps("f_b_many_contigs_one_penalty_each", tensors_,
+                  [(k, float(grid_[k % 64])) for k in range(args.contigs)], args.reps)
+    del tensors_
+    torch.cuda.empty_cache()
+    if not args.skip_long:
+        cs, ce, cnt = synthetic.poisson_coverage(10 ** 6, seed=1)
+        long_t = expand(cnt, (ce - cs).astype(np.int64))[:25 * 10 ** 6]
+        features_laps("f_a_first_2.5e7_bases_4_penalties", [long_t],
+                      [(0, 0.72), (0, 37.3), (0, 1550.5), (0, 51795.0)], args.reps)
+
+
 if args.reads:
     reads_mode()
+    sys.exit(0)
+if args.features:
+    features_mode()
     sys.exit(0)
 if args.labels:
     labels_mode()
