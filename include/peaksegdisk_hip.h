@@ -52,6 +52,15 @@ extern "C" {
                                       rank outside 0 .. bases - 1 of its contig; the contig and the
                                       rank are in peakseg_hip_last_error() */
 
+#define ERROR_FIT_ARGUMENTS 21     /* a penalty model that cannot be fitted: a shape outside the
+                                      limits, a feature that is not finite, a NaN limit, lo > hi, a
+                                      row with both limits infinite, a fold outside [0, F) or one
+                                      that leaves no training row, regularizations that are negative
+                                      or do not increase, a gram_lambda_max, threshold or
+                                      max_iterations that is not positive; the argument and the row
+                                      are in peakseg_hip_last_error().  The Python layer raises the
+                                      same status when no regularization has all its fits converged */
+
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
  *                               per GPU sets it from its rank
@@ -496,6 +505,48 @@ int peakseg_hip_coverage_stats_max_ranks(void);
 int peakseg_hip_coverage_stats_last_ms(float *ms);
 /* the digit passes the calling thread's last pack_coverage_stats launched (0: moments only) */
 int peakseg_hip_coverage_stats_last_passes(int *digit_passes);
+
+/* The fits of a penalty-learning regression (the model that penalty_model= takes): interval
+ * regression with the squared hinge of margin 1, an L1 penalty on the weights and an unpenalised
+ * intercept, for every regularization of a path and every fold of a cross-validation, in one launch
+ * of one workgroup per problem.  The call is not tied to a problem set.
+ *   rows      n (2 to 2^20 - 1), each with p (0 to peakseg_hip_penalty_fit_max_features())
+ *             standardised features, x_std[j * n + i] for feature j of row i (feature-major), and the
+ *             target [lo[i], hi[i]] in log(penalty); lo = -inf or hi = +inf is allowed, not both
+ *   folds     fold[i] in [0, n_folds), n_folds = F from 1 to 16.  Problem (f, k), f < F, trains on the
+ *             rows whose fold is not f with reg[k] and is validated on the rows of fold f; problem
+ *             (F, k) trains on all rows and is validated on them.  F = 1: no validation -- the
+ *             all-rows problem alone runs (every fold[i] is 0) and n_reg must be 1
+ *   reg       n_reg (1 to 256) increasing regularizations, none negative
+ *   objective (1/|S|) sum over the training rows S of phi(f_i - lo_i) + phi(hi_i - f_i)
+ *             + reg |w|_1, with f_i = b + w . x_i and phi(z) = (z - 1)^2 for z < 1, else 0
+ *   solver    accelerated proximal gradient from w = 0, b = 0 with the constant step
+ *             |S| / (4 gram_lambda_max) and a restart of the momentum; gram_lambda_max bounds the
+ *             largest eigenvalue of [X 1]'[X 1] over all rows from above (the caller computes it)
+ *   stopping  c = max(|dF/db|, max_j c_j) <= threshold, with c_j = |g_j + reg sign(w_j)| where
+ *             w_j != 0 and max(0, |g_j| - reg) where w_j = 0, g the gradient of the smooth part at the
+ *             weights returned; evaluated every 8 iterations and after max_iterations
+ * The outputs (any may be NULL) have one entry per problem, problem (f, k) at f * n_reg + k, in all
+ * (F + 1) * n_reg of them -- n_reg when F = 1: weights_out p + 1 doubles each, the intercept last, in
+ * standardised units; iterations_out; criterion_out, the c of the weights returned; converged_out, 1
+ * or 0 (max_iterations reached with c above threshold); incorrect_out, the validation rows whose
+ * prediction lies outside their interval; hinge_out, the sum of phi(f_i - lo_i) + phi(hi_i - f_i)
+ * over the validation rows.  Every floating-point sum has an order fixed by (n, p): two calls with
+ * the same arguments return the same bits.
+ * Returns 0; ERROR_FIT_ARGUMENTS with the argument and the row in peakseg_hip_last_error, checked on
+ * the host before anything is launched; then ERROR_NO_HIP_DEVICE.  Everything the call allocates on
+ * the device is freed before it returns. */
+int peakseg_hip_penalty_fit(int device, int n, int p, const double *x_std, const double *lo,
+                            const double *hi, const int *fold, int n_folds, int n_reg,
+                            const double *reg, double gram_lambda_max, double threshold,
+                            int max_iterations, double *weights_out, int *iterations_out,
+                            double *criterion_out, int *converged_out, long long *incorrect_out,
+                            double *hinge_out);
+/* milliseconds (HIP events) of the calling thread's last penalty_fit: zeroing and the launch, the
+ * upload excluded */
+int peakseg_hip_penalty_fit_last_ms(float *ms);
+/* the largest p of one call */
+int peakseg_hip_penalty_fit_max_features(void);
 
 /* Where a round of the parallel penalty search looks besides its secant penalty: up to `extras`
  * penalties between over_penalty (the bracket's smaller penalty, 0 allowed) and under_penalty (its

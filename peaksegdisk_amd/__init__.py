@@ -14,6 +14,8 @@ from .api import (PeakSegError, PeakSegFPOP_dir, PeakSegFPOP_df, PeakSegFPOP_fil
                   predict_penalties)
 from ._native import last_fanout  # noqa: F401
 from .grid import ProblemSet, read_labels_bed, features_from_stats  # noqa: F401
+from .fit import (PenaltyModelFit, fit_penalty_model, learn_penalty_model_dense,  # noqa: F401
+                  learn_penalty_model_reads)
 
 __all__ = ["PeakSegFPOP_file", "PeakSegFPOP_dir", "PeakSegFPOP_df", "PeakSegFPOP_vec",
            "PeakSegFPOP_dense", "PeakSegFPOP_reads", "coverage_from_reads",
@@ -23,4 +25,6 @@ __all__ = ["PeakSegFPOP_file", "PeakSegFPOP_dir", "PeakSegFPOP_df", "PeakSegFPOP
            "ProblemSet", "last_fanout", "read_labels_bed", "targetInterval_dense",
            "targetInterval_reads", "problem_features_dense", "problem_features_reads",
            "predict_penalties", "features_from_stats",
+           "fit_penalty_model", "learn_penalty_model_dense", "learn_penalty_model_reads",
+           "PenaltyModelFit",
            "PeakSegError"]

@@ -17,6 +17,7 @@ ERROR_DENSE_ARGUMENTS = 17
 ERROR_READS_ARGUMENTS = 18
 ERROR_LABEL_ARGUMENTS = 19
 ERROR_FEATURE_ARGUMENTS = 20
+ERROR_FIT_ARGUMENTS = 21
 
 
 class PsdResult(ctypes.Structure):
@@ -230,6 +231,15 @@ def declare(lib):
     lib.peakseg_hip_coverage_stats_last_ms.restype = c.c_int
     lib.peakseg_hip_coverage_stats_last_passes.argtypes = [c.POINTER(c.c_int)]
     lib.peakseg_hip_coverage_stats_last_passes.restype = c.c_int
+    lib.peakseg_hip_penalty_fit.argtypes = [
+        c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int,
+        c.c_void_p, c.c_double, c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_penalty_fit.restype = c.c_int
+    lib.peakseg_hip_penalty_fit_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_penalty_fit_last_ms.restype = c.c_int
+    lib.peakseg_hip_penalty_fit_max_features.argtypes = []
+    lib.peakseg_hip_penalty_fit_max_features.restype = c.c_int
     lib.peakseg_hip_search_place_penalties.argtypes = [
         c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
     lib.peakseg_hip_search_place_penalties.restype = c.c_int
@@ -271,6 +281,8 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_packed_coverage_stats_download",
     "peakseg_hip_coverage_stats_tile_runs", "peakseg_hip_coverage_stats_max_ranks",
     "peakseg_hip_coverage_stats_last_ms", "peakseg_hip_coverage_stats_last_passes",
+    "peakseg_hip_penalty_fit", "peakseg_hip_penalty_fit_last_ms",
+    "peakseg_hip_penalty_fit_max_features",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -86,6 +86,8 @@
 #include "label_errors.h"
 /* order statistics and moments of every contig's coverage from the resident runs */
 #include "coverage_stats.h"
+/* the fits of a penalty-learning regression over a regularisation path and the folds */
+#include "penalty_fit.h"
 
 #include <ctype.h>
 #include <errno.h>
@@ -123,6 +125,7 @@
 #include "peakseg_reads.h"
 #include "peakseg_labels.h"
 #include "peakseg_features.h"
+#include "peakseg_fit.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -490,6 +493,12 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
                 "error code %d: coverage statistics that cannot be computed (a negative number of "
                 "ranks or more than peakseg_hip_coverage_stats_max_ranks, or a rank outside "
                 "0 .. bases - 1 of its contig)", status);
+    PSD_MESSAGE(ERROR_FIT_ARGUMENTS,
+                "error code %d: a penalty model that cannot be fitted (a bad shape, a feature that is "
+                "not finite, a NaN limit or lo > hi, a row with both limits infinite, a fold outside "
+                "its range or one that leaves no training row, regularizations that do not increase, "
+                "a gram_lambda_max, threshold or max_iterations that is not positive -- or no "
+                "regularization whose fits all converged)", status);
     default:
       snprintf(buf, buf_len, "error code %d", status);
       break;
