@@ -60,6 +60,11 @@ extern "C" {
                                       max_iterations that is not positive; the argument and the row
                                       are in peakseg_hip_last_error().  The Python layer raises the
                                       same status when no regularization has all its fits converged */
+#define ERROR_REGION_ARGUMENTS 22  /* regions or groups that cannot be served: a negative number of
+                                      regions or groups, a NULL or misaligned array, a region with
+                                      chromStart >= chromEnd, a problem in a group outside
+                                      -1 .. n_groups - 1; the contig and the region, or the problem,
+                                      are in peakseg_hip_last_error() */
 
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
@@ -506,6 +511,83 @@ int peakseg_hip_coverage_stats_last_ms(float *ms);
 /* the digit passes the calling thread's last pack_coverage_stats launched (0: moments only) */
 int peakseg_hip_coverage_stats_last_passes(int *digit_passes);
 
+/* The coverage of caller-chosen regions of every contig of a set made from dense counts or reads,
+ * computed on the device from the resident runs (what bigWigAverageOverBed does for a bigWig).
+ * A region is [chromStart, chromEnd) in BED coordinates; contig c covers
+ * [first_chromStart[c], first_chromStart[c] + bases).  Regions come in any order, may overlap one
+ * another, and may lie partly or wholly outside their contig.  Per region:
+ *   bases  int32  the bases of the region that lie inside the contig
+ *   sum    int64  the sum of the per-base counts over those bases: sum of count_i x |run_i in the
+ *                 region|; a run cut by an edge of the region counts with the cut length only
+ *   max    int32  the largest count_i of a run that meets the region; 0 where bases == 0
+ * first_chromStart: one per CONTIG, NULL = zeros (the check of pack_segments).  n_regions[c]: the
+ * regions of contig c; region_start / region_end: per contig an int32 array of that many entries
+ * (not read where n_regions[c] == 0); regions_on_device != 0: the arrays are device addresses
+ * (multiples of 4) and are read in place, else host memory that the library uploads.  rows_out[c]
+ * (n_contigs entries, host, may be NULL) receives contig c's row count, n_regions[c].  The packed
+ * columns hold the contigs' regions one contig after the other, in the order given.  Integer
+ * arithmetic only: the same whatever the schedule.  The set may be solved or not, and the call
+ * leaves what a solve made (the segment tables, the packed columns) as it is.  Three launches,
+ * however many contigs and regions there are (peaksegdisk_amd/csrc/region_stats.h).
+ * Returns the total number of rows; -1 for a set that was not made from dense counts or reads;
+ * -ERROR_REGION_ARGUMENTS for what that status names (host arrays are checked on the host, device
+ * arrays by the first launch, after which nothing further is launched); the text is in
+ * peakseg_hip_last_error.  The device addresses stay valid until this function is called again or
+ * the set is destroyed; ..._download copies the columns (any may be NULL) to host arrays and
+ * returns -1 when there is nothing packed. */
+long long peakseg_hip_problem_set_pack_region_stats(
+    psd_problem_set *set, const int *first_chromStart, const long long *n_regions,
+    const int *const *region_start, const int *const *region_end, int regions_on_device,
+    long long *rows_out, const int **bases_dev, const long long **sum_dev, const int **max_dev);
+int peakseg_hip_problem_set_packed_region_stats_download(psd_problem_set *set, int *bases_out,
+                                                         long long *sum_out, int *max_out);
+/* the tile of the fold: runs one workgroup folds for one region at a time, laid over the contig's
+ * 16-byte aligned range as pack_segment_stats' tiles are (tests aim at its boundaries) */
+int peakseg_hip_region_stats_tile_runs(void);
+/* milliseconds (HIP events) of the calling thread's last pack_region_stats: the launches */
+int peakseg_hip_region_stats_last_ms(float *ms);
+
+/* Which peaks of several models are the same peak, and what every model has under each of them:
+ * the consensus peaks of the samples of a genomic region (PeakSegPipeline's clusterPeaks) and the
+ * cluster-by-sample matrix that differential analysis starts from.  For a SOLVED set made from
+ * dense counts or reads.  group[p] (n_problems entries, host) is in [-1, n_groups): -1 keeps
+ * problem p out.  The members of a group are its problems in increasing problem index; a group may
+ * be empty.  A member's peaks are the odd rows [ps, pe) of its segments table in genomic
+ * coordinates (its contig's first_chromStart added; a model of one segment has none); members of
+ * one group may have different first_chromStart and lengths, and may share a contig.
+ *   clusters  two peaks overlap when ps_a < pe_b && ps_b < pe_a (abutting peaks do not); the
+ *             clusters of a group are the connected components of that relation over all peaks of
+ *             all its members.  Four int32 per cluster: clusterStart (the smallest ps), clusterEnd
+ *             (the largest pe), peaks (the peaks joined), samples (the members with a peak in it).
+ *             Packed group after group, within a group in INCREASING clusterStart -- the segments
+ *             tables themselves are in decreasing order
+ *   matrix    for a group of m members and k clusters k x m entries, cluster-major, the members in
+ *             member order, group after group: m_peaks (int32, the member's peaks with
+ *             ps < clusterEnd && clusterStart < pe) and m_bases / m_sum / m_max: the three columns
+ *             of pack_region_stats with the cluster as a region of the member's contig
+ * clusters_out[g], members_out[g] (n_groups entries, host, may be NULL) receive k and m of group g.
+ * Integer arithmetic only: the same whatever the schedule.  The number of launches does not depend
+ * on the numbers of problems, groups, members or peaks; the groups' cluster counts are downloaded
+ * once in between (peaksegdisk_amd/csrc/peak_clusters.h).
+ * Returns the total number of clusters; -1 for a set that is not solved or was not made from dense
+ * counts; -ERROR_REGION_ARGUMENTS for n_groups < 0 or a group value outside [-1, n_groups), with
+ * the problem named; -ERROR_DEVICE_MEMORY for a matrix that does not fit (PEAKSEG_HIP_MAX_BYTES or
+ * the device), said before anything of it is written; the text is in peakseg_hip_last_error.  The
+ * device addresses stay valid until the set is solved again, this function is called again, or the
+ * set is destroyed; ..._download copies the columns (any may be NULL) to host arrays and returns -1
+ * when there is nothing packed. */
+long long peakseg_hip_problem_set_pack_peak_clusters(
+    psd_problem_set *set, const int *first_chromStart, int n_groups, const int *group,
+    long long *clusters_out, long long *members_out, const int **clusterStart_dev,
+    const int **clusterEnd_dev, const int **peaks_dev, const int **samples_dev, const int **m_peaks_dev,
+    const int **m_bases_dev, const long long **m_sum_dev, const int **m_max_dev);
+int peakseg_hip_problem_set_packed_peak_clusters_download(
+    psd_problem_set *set, int *clusterStart_out, int *clusterEnd_out, int *peaks_out, int *samples_out,
+    int *m_peaks_out, int *m_bases_out, long long *m_sum_out, int *m_max_out);
+/* milliseconds (HIP events) of the calling thread's last pack_peak_clusters: from its first launch
+ * to its last, the download of the groups' cluster counts included */
+int peakseg_hip_peak_clusters_last_ms(float *ms);
+
 /* The fits of a penalty-learning regression (the model that penalty_model= takes): interval
  * regression with the squared hinge of margin 1, an L1 penalty on the weights and an unpenalised
  * intercept, for every regularization of a path and every fold of a cross-validation, in one launch
@@ -612,6 +694,19 @@ int peakseg_hip_reads_pileup_probe(int device, int n_contigs, const long long *n
 /* milliseconds (HIP events) of the calling thread's last pile-up: zeroing and scatter_kernel; the
  * three launches of the prefix sum */
 int peakseg_hip_reads_last_pileup_ms(float *scatter_ms, float *scan_ms);
+
+/* Tests: the cluster kernels alone, on caller-given peaks of the members of ONE group, without any
+ * solve.  n_peaks[m]: the peaks of member m; peak_start[m] / peak_end[m]: host int32 arrays, sorted
+ * and disjoint (peak_end[i] <= peak_start[i + 1]), coordinates in [0, 2^31).  clusterStart_out /
+ * clusterEnd_out / peaks_out / samples_out (room for one entry per peak: there are no more clusters
+ * than peaks) receive the cluster table in increasing clusterStart, m_peaks_out (clusters x
+ * n_members entries, cluster-major; room for peaks x n_members) the matrix' peaks column; any may
+ * be NULL.  Returns the clusters; -ERROR_REGION_ARGUMENTS for lists that are not as said (the member
+ * and the peak are in peakseg_hip_last_error), -ERROR_NO_HIP_DEVICE, or -1. */
+long long peakseg_hip_peak_clusters_probe(int device, int n_members, const long long *n_peaks,
+                                          const int *const *peak_start, const int *const *peak_end,
+                                          int *clusterStart_out, int *clusterEnd_out, int *peaks_out,
+                                          int *samples_out, int *m_peaks_out);
 
 /* Tests: R's paste() of a double (15 significant digits) as the penalty search and the timing
  * files format numbers; returns the length. */

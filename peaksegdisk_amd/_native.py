@@ -18,6 +18,7 @@ ERROR_READS_ARGUMENTS = 18
 ERROR_LABEL_ARGUMENTS = 19
 ERROR_FEATURE_ARGUMENTS = 20
 ERROR_FIT_ARGUMENTS = 21
+ERROR_REGION_ARGUMENTS = 22
 
 
 class PsdResult(ctypes.Structure):
@@ -240,6 +241,30 @@ def declare(lib):
     lib.peakseg_hip_penalty_fit_last_ms.restype = c.c_int
     lib.peakseg_hip_penalty_fit_max_features.argtypes = []
     lib.peakseg_hip_penalty_fit_max_features.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_region_stats.argtypes = [
+        c.c_void_p, c.c_void_p, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p), c.c_int, c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_pack_region_stats.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_region_stats_download.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_problem_set_packed_region_stats_download.restype = c.c_int
+    lib.peakseg_hip_region_stats_tile_runs.argtypes = []
+    lib.peakseg_hip_region_stats_tile_runs.restype = c.c_int
+    lib.peakseg_hip_region_stats_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_region_stats_last_ms.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_peak_clusters.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p] + \
+        [c.POINTER(c.c_void_p)] * 8
+    lib.peakseg_hip_problem_set_pack_peak_clusters.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_peak_clusters_download.argtypes = [c.c_void_p] * 9
+    lib.peakseg_hip_problem_set_packed_peak_clusters_download.restype = c.c_int
+    lib.peakseg_hip_peak_clusters_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_peak_clusters_last_ms.restype = c.c_int
+    lib.peakseg_hip_peak_clusters_probe.argtypes = [
+        c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.peakseg_hip_peak_clusters_probe.restype = c.c_longlong
     lib.peakseg_hip_search_place_penalties.argtypes = [
         c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
     lib.peakseg_hip_search_place_penalties.restype = c.c_int
@@ -283,6 +308,12 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_coverage_stats_last_ms", "peakseg_hip_coverage_stats_last_passes",
     "peakseg_hip_penalty_fit", "peakseg_hip_penalty_fit_last_ms",
     "peakseg_hip_penalty_fit_max_features",
+    "peakseg_hip_problem_set_pack_region_stats",
+    "peakseg_hip_problem_set_packed_region_stats_download",
+    "peakseg_hip_region_stats_tile_runs", "peakseg_hip_region_stats_last_ms",
+    "peakseg_hip_problem_set_pack_peak_clusters",
+    "peakseg_hip_problem_set_packed_peak_clusters_download",
+    "peakseg_hip_peak_clusters_last_ms", "peakseg_hip_peak_clusters_probe",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -397,12 +397,15 @@ def _label_frame(chrom, entry, columns):
 LABEL_TOTALS = ["errors", "fp", "fn", "possible.fp", "possible.fn"]
 
 
-def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, penalty_model=None):
+def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, penalty_model=None,
+                     cluster_groups=None):
     """What PeakSegFPOP_dense and PeakSegFPOP_reads share: the problems of `pens` (one list per
     contig), the set -- make_set(problems) -> (ProblemSet, chromStart of each contig's first
     base) --, its solution, and the reference's data frames, nested as `pens` is.
     penalty_model: `pens` holds one placeholder (Inf) per contig; every problem gets the penalty
-    the model predicts from the set's coverage features before the one solve."""
+    the model predicts from the set's coverage features before the one solve.
+    cluster_groups: one group per problem; the solved set's ProblemSet.peak_clusters() is returned
+    with the data frames, as (frames, clusters)."""
     if labels is not None:
         labels = _label_lists(labels, len(pens), single, "contig")
     problems, pen_strs = [], []
@@ -438,6 +441,12 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, p
         if labels is not None:
             try:
                 label_totals, label_cols = pset.label_errors(labels, first_chromStart=chrom_starts)
+            except RuntimeError as e:
+                raise PeakSegError(getattr(e, "status", _native.ERROR_DEVICE_SOLVER), str(e))
+        clusters = None
+        if cluster_groups is not None:
+            try:
+                clusters = pset.peak_clusters(cluster_groups, first_chromStart=chrom_starts)
             except RuntimeError as e:
                 raise PeakSegError(getattr(e, "status", _native.ERROR_DEVICE_SOLVER), str(e))
         rows = [(pset.loss(p), pset.result(p)) for p in range(len(problems))]
@@ -478,7 +487,8 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, p
     for q in pens:
         out.append(flat[o:o + len(q)])
         o += len(q)
-    return out[0] if single else out
+    out = out[0] if single else out
+    return out if cluster_groups is None else (out, clusters)
 
 
 def _penalty_source(penalties, penalty_model, n_contigs, noun):
@@ -576,6 +586,138 @@ def PeakSegFPOP_reads(reads, penalties=None, chrom="chrUnknown", extents=None, b
         return pset, pset.contig_starts
     return _solve_dense_set(make_set, pens, chrom, stats, single, "<aligned reads>", labels,
                             penalty_model)
+
+
+# ---- consensus peaks of several samples (additive) ---------------------
+
+class ConsensusPeaks:
+    """What consensus_peaks_dense / consensus_peaks_reads return.
+    groups: a list over groups of {"samples": the indices of the group's samples, "clusters": a data
+    frame chrom, clusterStart, clusterEnd, peaks, samples -- the consensus peaks in increasing
+    clusterStart --, "peaks", "bases", "sum", "max": (clusters, samples of the group) arrays};
+    fits: a list over samples of PeakSegFPOP_dir_result, each sample's own model.
+    clusters, peaks, bases, sum, max: those of the only group (ValueError when there are several)."""
+
+    def __init__(self, groups, fits):
+        self.groups = groups
+        self.fits = fits
+
+    def _only(self, name):
+        if len(self.groups) != 1:
+            raise ValueError("%d groups: read .groups[g][%r]" % (len(self.groups), name))
+        return self.groups[0][name]
+
+    clusters = property(lambda self: self._only("clusters"))
+    peaks = property(lambda self: self._only("peaks"))
+    bases = property(lambda self: self._only("bases"))
+    sum = property(lambda self: self._only("sum"))
+    max = property(lambda self: self._only("max"))
+
+
+def _consensus_arguments(n_samples, penalties, penalty_model, groups, chrom):
+    """(pens of _solve_dense_set, groups int32[n_samples], chrom per group) of the consensus
+    entries, checked before any device work in the style of _label_lists"""
+    if n_samples == 0:
+        raise ValueError("consensus peaks: at least one sample")
+    if penalties is not None and not isinstance(penalties, (int, float, np.integer, np.floating)):
+        penalties = list(penalties)
+        if len(penalties) != n_samples:
+            raise ValueError("penalties: one per sample (%d penalties, %d samples)"
+                             % (len(penalties), n_samples))
+        for q in penalties:
+            if isinstance(q, (list, tuple, np.ndarray)):
+                raise ValueError("penalties: one number per sample, not a list per sample")
+        penalties = [[q] for q in penalties]
+    elif penalties is not None:
+        penalties = [[penalties]] * n_samples
+    pens = _penalty_source(penalties, penalty_model, n_samples, "sample")
+    if groups is None:
+        groups = np.zeros(n_samples, dtype=np.int32)
+    else:
+        given = np.asarray(groups)
+        if given.shape != (n_samples,):
+            raise ValueError("groups: one per sample (%d values, %d samples)" % (given.size, n_samples))
+        if not np.issubdtype(given.dtype, np.integer):
+            raise ValueError("groups must be integers")
+        if given.min() < -1:
+            bad = int(np.flatnonzero(given < -1)[0])
+            raise ValueError("groups: sample %d is in group %d; -1 is no group" % (bad, given[bad]))
+        groups = given.astype(np.int32)
+    n_groups = int(groups.max()) + 1
+    if isinstance(chrom, str):
+        chrom = [chrom] * n_groups
+    elif len(chrom) != n_groups:
+        raise ValueError("chrom: one name, or one per group (%d names, %d groups)"
+                         % (len(chrom), n_groups))
+    return pens, groups, list(chrom)
+
+
+def _consensus_result(solved, groups, chrom):
+    fits, clusters = solved
+    out = []
+    for g, entry in enumerate(clusters):
+        frame = entry["clusters"].copy()
+        frame.insert(0, "chrom", chrom[g])
+        out.append({"samples": entry["members"], "clusters": frame, "peaks": entry["peaks"],
+                    "bases": entry["bases"], "sum": entry["sum"], "max": entry["max"]})
+    fits = [f[0] for f in fits]
+    for fit, g in zip(fits, groups.tolist()):
+        if g >= 0:
+            fit.segments["chrom"] = chrom[g]
+    return ConsensusPeaks(out, fits)
+
+
+def consensus_peaks_dense(count_vecs, penalties=None, penalty_model=None, groups=None,
+                          chrom="chrUnknown", chrom_starts=None, device=0):
+    """Samples in, consensus peaks and count matrix out, in one process and without a table leaving
+    the device in between: every sample's dense coverage (count_vecs: a list of vectors as
+    PeakSegFPOP_dense takes them, one per sample) is encoded and solved as one problem, the peaks of
+    the samples of a group are clustered (ProblemSet.peak_clusters: two peaks are one consensus peak
+    when a chain of overlapping peaks joins them), and every sample's coverage under every consensus
+    peak is summed -- all on the GPU.  penalties: one number for all samples or one per sample;
+    penalty_model instead: a fitted model as PeakSegFPOP_dense takes it (exactly one of the two).
+    groups: one integer per sample, the genomic region it covers (-1: in none); None: all samples are
+    one group.  chrom: one name, or one per group; chrom_starts: the coordinate of each sample's
+    first base (default 0): samples of a group may begin and end at different coordinates.
+    Returns a ConsensusPeaks."""
+    from .grid import ProblemSet
+    if isinstance(count_vecs, np.ndarray) and count_vecs.ndim == 1 or hasattr(count_vecs, "data_ptr"):
+        raise ValueError("count.vecs: a list of vectors, one per sample")
+    vecs = list(count_vecs)
+    pens, groups, chrom = _consensus_arguments(len(vecs), penalties, penalty_model, groups, chrom)
+    contigs = [_int32_vector(v) for v in vecs]
+    if chrom_starts is None:
+        chrom_starts = [0] * len(vecs)
+    if len(chrom_starts) != len(vecs):
+        raise ValueError("chrom.starts: one per sample")
+    solved = _solve_dense_set(
+        lambda problems: (ProblemSet.from_dense(contigs, problems, device=device), chrom_starts),
+        pens, "chrUnknown", False, False, "<dense counts>", None, penalty_model, cluster_groups=groups)
+    return _consensus_result(solved, groups, chrom)
+
+
+def consensus_peaks_reads(reads, penalties=None, penalty_model=None, groups=None, chrom="chrUnknown",
+                          extents=None, bases_counted="each", device=0):
+    """consensus_peaks_dense with the pile-up in front of it: reads is a list over samples of
+    (chromStart, chromEnd) or (chromStart, chromEnd, count) as PeakSegFPOP_reads takes them;
+    extents, bases_counted as there.  Coordinates are genomic: a sample's first base is its extent's
+    chromStart."""
+    from .grid import ProblemSet
+    if len(reads) and not isinstance(reads[0], (tuple, list)):
+        raise ValueError("reads: a list of samples, each (chromStart, chromEnd[, count])")
+    samples = list(reads)
+    pens, groups, chrom = _consensus_arguments(len(samples), penalties, penalty_model, groups, chrom)
+    names = ("chromStart", "chromEnd", "count")
+    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
+               for entry in samples]
+
+    def make_set(problems):
+        pset = ProblemSet.from_reads(contigs, problems, extents=extents,
+                                     bases_counted=bases_counted, device=device)
+        return pset, pset.contig_starts
+    solved = _solve_dense_set(make_set, pens, "chrUnknown", False, False, "<aligned reads>", None,
+                              penalty_model, cluster_groups=groups)
+    return _consensus_result(solved, groups, chrom)
 
 
 # ---- coverage features and learned penalties (additive; DESIGN.md section 13) ----------------

@@ -104,7 +104,7 @@ PSD_COLD_DEV unsigned long long arena_take(const DeviceArgs &a, int n) {
           break;
         }
         if (final_now || cycle_now() - t_wait > LIVE_WAIT_CYCLES) break;
-        spin_pause();
+        host_pause();
       }
       if (!mapped) return ~0ull;
       /* a block the host added during this launch: its address goes into the device table */

@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -88,6 +88,10 @@
 #include "coverage_stats.h"
 /* the fits of a penalty-learning regression over a regularisation path and the folds */
 #include "penalty_fit.h"
+/* the coverage of any regions from the resident runs: bases, sum and maximum */
+#include "region_stats.h"
+/* the clusters of overlapping peaks over the members of a group, and the cluster-by-member matrix */
+#include "peak_clusters.h"
 
 #include <ctype.h>
 #include <errno.h>
@@ -126,6 +130,8 @@
 #include "peakseg_labels.h"
 #include "peakseg_features.h"
 #include "peakseg_fit.h"
+#include "peakseg_regions.h"
+#include "peakseg_clusters.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -177,6 +183,9 @@ extern "C" void peakseg_hip_problem_set_destroy(psd_problem_set *s) {
     if (e) (void)hipEventDestroy(e);
   for (auto &e : s->features.ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto *ev : {s->regions.ev, s->clusters.ev, s->clusters.matrix.ev})
+    for (int k = 0; k < 2; k++)
+      if (ev[k]) (void)hipEventDestroy(ev[k]);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   if (s->stream2) (void)hipStreamDestroy(s->stream2);
   if (s->started) (void)hipHostFree(s->started);
@@ -499,6 +508,10 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
                 "its range or one that leaves no training row, regularizations that do not increase, "
                 "a gram_lambda_max, threshold or max_iterations that is not positive -- or no "
                 "regularization whose fits all converged)", status);
+    PSD_MESSAGE(ERROR_REGION_ARGUMENTS,
+                "error code %d: regions or groups that cannot be served (a negative number of regions "
+                "or groups, a NULL or misaligned array, a region with chromStart >= chromEnd, or a "
+                "problem in a group outside -1 .. n_groups - 1)", status);
     default:
       snprintf(buf, buf_len, "error code %d", status);
       break;

@@ -81,6 +81,48 @@ struct FeatureTable {
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
+/* What peakseg_hip_problem_set_pack_region_stats keeps (peakseg_regions.h): the regions of a call
+ * with host arrays, the contigs' descriptors and check words, what locate_kernel leaves for
+ * fold_kernel (spans and the two levels of prefix sums), and the packed columns.  Every array grows
+ * to what the largest call so far needed.  The cluster-by-member matrix has a table of its own. */
+struct RegionTable {
+  int *d_regions = nullptr;                  /* 2 x regions: start, end (host arrays only) */
+  psd::regions::Contig *d_contigs = nullptr; /* per contig */
+  long long *d_reg_off = nullptr;            /* n_contigs + 1 */
+  unsigned long long *d_check = nullptr;     /* per contig */
+  psd::regions::Span *span = nullptr;        /* per region */
+  int *off = nullptr;                        /* per region */
+  long long *block_sum = nullptr;            /* per workgroup of locate_kernel, and the total */
+  int *bases = nullptr, *mx = nullptr;       /* per region: the packed columns */
+  long long *sum = nullptr;
+  long long capacity = 0;
+  long long total = -1; /* regions of the last call (-1: nothing packed) */
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+/* What peakseg_hip_problem_set_pack_peak_clusters keeps (peakseg_clusters.h): the members and
+ * groups of a call, the members' peaks, the flags' prefix sums, the cluster table, the groups'
+ * cluster counts, and the matrix with the regions its entries are.  Every array grows to what the
+ * largest call so far needed. */
+struct ClusterTable {
+  psd::clusters::Member *members = nullptr;                     /* per member */
+  long long *member_off = nullptr;                              /* members + 1 */
+  int *member_group = nullptr, *member_contig = nullptr;        /* per member */
+  int *group_member0 = nullptr;                                 /* groups + 1 */
+  long long *group_clusters = nullptr, *entry_off = nullptr, *cluster_off = nullptr; /* groups + 1 */
+  long long member_capacity = 0, group_capacity = 0;
+  int *peak_start = nullptr, *peak_end = nullptr, *lead = nullptr, *off = nullptr; /* per peak (+ 1) */
+  long long *block_sum = nullptr;
+  int *cluster_start = nullptr, *cluster_end = nullptr, *cluster_peaks = nullptr,
+      *cluster_samples = nullptr; /* per cluster: at most one per peak */
+  long long peak_capacity = 0;
+  int *m_peaks = nullptr, *region_start = nullptr, *region_end = nullptr, *region_contig = nullptr;
+  long long entry_capacity = 0;
+  RegionTable matrix;   /* bases, sum and max of the entries */
+  long long clusters = -1, entries = -1; /* of the last call (-1: nothing packed) */
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
 struct psd_problem_set {
   /* geometry: the contigs, the problems and where their tables start */
   int device = 0;
@@ -145,6 +187,8 @@ struct psd_problem_set {
   StatsTable stats; /* (sets made from dense counts) */
   LabelTable labels; /* (sets made from dense counts) */
   FeatureTable features; /* (sets made from dense counts) */
+  RegionTable regions; /* (sets made from dense counts) */
+  ClusterTable clusters; /* (sets made from dense counts) */
 
   /* Sets made from dense counts (peakseg_hip_problem_set_create_dense): run_end[] next to count[]
    * and weight[], the sum of each contig's counts, and which contigs are constant.  Their trivial

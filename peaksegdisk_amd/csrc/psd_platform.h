@@ -16,6 +16,7 @@
 
 #ifdef PSD_EMU
 #include "hip_emu.h"
+#include <time.h>
 #define PSD_D static inline
 #define PSD_M inline
 #define PSD_NOINLINE static __attribute__((noinline))
@@ -124,6 +125,16 @@ PSD_D __attribute__((nodebug)) long long cycle_now() {
 PSD_D int flag_load(const int *p) { return *(const volatile int *)p; }
 PSD_D void flag_store(int *p, int v) { *(volatile int *)p = v; }
 PSD_D void spin_pause() { emu::yield_fiber(); }
+/* between two polls of a word that a HOST thread writes while the kernel runs (the arena's growth).
+ * The emulator takes a block whose fibers did nothing but poll for 64 rounds -- well under a
+ * millisecond -- for deadlocked; a host thread that has not been given a core yet loses that race.
+ * So the poll also gives up the core for a moment: 64 rounds of a wave's lanes are a quarter of a
+ * second of patience at least. */
+PSD_D void host_pause() {
+  emu::yield_fiber();
+  const struct timespec moment = {0, 50000};
+  (void)nanosleep(&moment, nullptr);
+}
 PSD_D void device_fence() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 #else
 PSD_D int flag_load(const int *p) {
@@ -136,6 +147,8 @@ PSD_D void flag_store(int *p, int v) {
  * LDS cycles from the waves at work (-1.2 %), and longer sleeps ended by s_wakeup from the
  * posting wave are slower still (-2 % to -4 %): profiles/r02/ab_step_barrier.log */
 PSD_D void spin_pause() { __builtin_amdgcn_s_sleep(1); }
+/* between two polls of a word that a host thread writes while the kernel runs: the same pause */
+PSD_D void host_pause() { __builtin_amdgcn_s_sleep(1); }
 /* make this thread's global stores visible to the other waves of the device */
 PSD_D void device_fence() { __threadfence(); }
 #endif
@@ -179,6 +192,11 @@ PSD_D void atomic_max_u64(unsigned long long *p, unsigned long long v) {
   while (v > o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
   }
 }
+PSD_D void atomic_max_i32(int *p, int v) {
+  int o = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v > o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+  }
+}
 #else
 PSD_D void atomic_add_i32(int *p, int v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -187,6 +205,9 @@ PSD_D void atomic_add_i64(long long *p, long long v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 PSD_D void atomic_max_u64(unsigned long long *p, unsigned long long v) {
+  (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+PSD_D void atomic_max_i32(int *p, int v) {
   (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 #endif

@@ -470,6 +470,157 @@ class ProblemSet:
                                % self._lib.peakseg_hip_last_error().decode())
         return totals, [tuple(a[offs[p]:offs[p + 1]] for a in cols) for p in range(k)]
 
+    def _first_chromStart(self, first_chromStart):
+        if first_chromStart is None:
+            return None
+        first = np.ascontiguousarray(first_chromStart, dtype=np.int32)
+        if first.shape != (self._n_contigs(),):
+            raise ValueError("first_chromStart: one value per contig")
+        return first
+
+    def _raise_status(self, who, total):
+        err = RuntimeError("%s: %s" % (who, self._lib.peakseg_hip_last_error().decode()))
+        err.status = int(-total) if total < -1 else _native.ERROR_DEVICE_SOLVER
+        raise err
+
+    def region_stats(self, regions, first_chromStart=None, torch_device=None):
+        """The coverage of caller-chosen regions of every contig of a set made by from_dense or
+        from_reads (solved or not), computed on the device from the resident runs
+        (peakseg_hip_problem_set_pack_region_stats; bigWigAverageOverBed's job).  regions: a list
+        over CONTIGS of (chromStart, chromEnd) -- 1-d contiguous int32 numpy arrays or torch tensors
+        --, an empty entry (or None) for a contig without regions.  Regions come in any order, may
+        overlap, and may lie partly or wholly outside their contig; tensors on the set's cuda device
+        are read in place; one call takes one kind of memory.  first_chromStart as in
+        segment_columns().  Without torch_device: a list over contigs of {"bases": int32[],
+        "sum": int64[], "max": int32[]}, one entry per region in the order given: the bases of the
+        region inside the contig, the sum of the per-base counts over them, and the largest count
+        of a run that meets it.  With torch_device: (rows int64 numpy[n_contigs + 1], bases, sum,
+        max) where the three are tensors that alias the library's buffers: nothing is downloaded,
+        and they are valid until the next region_stats() or close().  A region with
+        chromStart >= chromEnd raises RuntimeError with .status 22, naming the contig and the
+        region."""
+        n_contigs = self._n_contigs()
+        if len(regions) != n_contigs:
+            raise ValueError("region_stats: one entry per contig (%d entries, %d contigs)"
+                             % (len(regions), n_contigs))
+        first = self._first_chromStart(first_chromStart)
+        names = ("chromStart", "chromEnd")
+        keep, sides, lengths = [], [], []
+        ptrs = ([], [])
+        for c, entry in enumerate(regions):
+            if entry is None or len(entry) == 0:
+                lengths.append(0)
+                for q in ptrs:
+                    q.append(0)
+                continue
+            if len(entry) != 2:
+                raise ValueError("region_stats: contig %d is not (chromStart, chromEnd)" % c)
+            n = None
+            for j in range(2):
+                ptr, m, side, ref = _dense_pointer(c, entry[j], self.device,
+                                                   "region_stats: contig %d " + names[j])
+                if n is not None and m != n:
+                    raise ValueError("region_stats: contig %d has %d chromStart and %d chromEnd"
+                                     % (c, n, m))
+                n = m
+                keep.append(ref)
+                sides.append((side, c))
+                ptrs[j].append(ptr if m else 0)
+            lengths.append(n)
+        for side, c in sides:
+            if side != sides[0][0]:
+                raise ValueError("region_stats: contig %d is in %s memory but contig %d is in %s "
+                                 "memory; one call takes one kind" % (c, side, sides[0][1], sides[0][0]))
+        out = [ctypes.c_void_p() for _ in range(3)]
+        total = self._lib.peakseg_hip_problem_set_pack_region_stats(
+            self._h, first.ctypes.data if first is not None else None,
+            (ctypes.c_longlong * n_contigs)(*lengths),
+            *[(ctypes.c_void_p * n_contigs)(*q) for q in ptrs],
+            1 if sides and sides[0][0] == "device" else 0, None, *[ctypes.byref(q) for q in out])
+        del keep  # (the library holds no reference to the caller's buffers after the call)
+        if total < 0:
+            self._raise_status("pack_region_stats", total)
+        total = int(total)
+        offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        dtypes = (np.int32, np.int64, np.int32)
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            return (offs,) + tuple(device_array(q.value or 0, total, dt, dev)
+                                   for q, dt in zip(out, dtypes))
+        cols = [np.empty(total, dtype=dt) for dt in dtypes]
+        if self._lib.peakseg_hip_problem_set_packed_region_stats_download(
+                self._h, *[a.ctypes.data for a in cols]) != 0:
+            raise RuntimeError("packed_region_stats_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        return [{name: a[offs[c]:offs[c + 1]] for name, a in zip(("bases", "sum", "max"), cols)}
+                for c in range(n_contigs)]
+
+    def peak_clusters(self, groups, first_chromStart=None, torch_device=None):
+        """Which peaks of the set's models are the same peak, and what every model has under each
+        of them (peakseg_hip_problem_set_pack_peak_clusters; include/peaksegdisk_hip.h has the
+        definitions), on the device from the resident tables of a solved set made by from_dense or
+        from_reads.  groups: one integer per PROBLEM, -1 (in no group) or a group 0 .. n_groups - 1;
+        n_groups is the largest value + 1.  The members of a group are its problems in increasing
+        index; two peaks belong to one cluster when a chain of overlapping peaks joins them.
+        first_chromStart as in segment_columns().  Without torch_device: a list over groups of
+        {"members": the problems' indices, "clusters": a data frame with the columns clusterStart,
+        clusterEnd, peaks, samples in increasing clusterStart, and "peaks", "bases", "sum", "max":
+        (clusters, members) arrays -- the member's peaks under the cluster, and the region_stats()
+        columns of the cluster as a region of the member's contig}.  With torch_device:
+        (clusters int64 numpy[n_groups + 1], entries int64 numpy[n_groups + 1], clusterStart,
+        clusterEnd, peaks, samples, m_peaks, m_bases, m_sum, m_max) where the eight are tensors that
+        alias the library's buffers (group g's clusters are clusters[g]:clusters[g + 1], its matrix
+        entries entries[g]:entries[g + 1], cluster-major); they are valid until the next solve(),
+        the next peak_clusters() or close()."""
+        group = np.ascontiguousarray(groups, dtype=np.int32) if len(groups) else np.zeros(0, np.int32)
+        if group.shape != (len(self.problems),):
+            raise ValueError("peak_clusters: one group per problem (%d values, %d problems)"
+                             % (group.size, len(self.problems)))
+        if not np.array_equal(group, np.asarray(groups)):
+            raise ValueError("peak_clusters: groups must be integers")
+        n_groups = int(group.max()) + 1 if group.size and group.max() >= 0 else 0
+        first = self._first_chromStart(first_chromStart)
+        k = np.zeros(max(n_groups, 1), dtype=np.int64)
+        m = np.zeros(max(n_groups, 1), dtype=np.int64)
+        out = [ctypes.c_void_p() for _ in range(8)]
+        total = self._lib.peakseg_hip_problem_set_pack_peak_clusters(
+            self._h, first.ctypes.data if first is not None else None, n_groups, group.ctypes.data,
+            k.ctypes.data, m.ctypes.data, *[ctypes.byref(q) for q in out])
+        if total < 0:
+            self._raise_status("pack_peak_clusters", total)
+        total = int(total)
+        k, m = k[:n_groups], m[:n_groups]
+        c_off = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
+        e_off = np.concatenate([[0], np.cumsum(k * m)]).astype(np.int64)
+        entries = int(e_off[-1])
+        dtypes = (np.int32,) * 6 + (np.int64, np.int32)
+        sizes = (total,) * 4 + (entries,) * 4
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            return (c_off, e_off) + tuple(device_array(q.value or 0, n, dt, dev)
+                                          for q, n, dt in zip(out, sizes, dtypes))
+        cols = [np.empty(n, dtype=dt) for n, dt in zip(sizes, dtypes)]
+        if self._lib.peakseg_hip_problem_set_packed_peak_clusters_download(
+                self._h, *[a.ctypes.data for a in cols]) != 0:
+            raise RuntimeError("packed_peak_clusters_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        import pandas as pd
+        result = []
+        for g in range(n_groups):
+            rows = slice(int(c_off[g]), int(c_off[g + 1]))
+            cells = slice(int(e_off[g]), int(e_off[g + 1]))
+            entry = {"members": np.flatnonzero(group == g),
+                     "clusters": pd.DataFrame({name: cols[j][rows] for j, name in enumerate(
+                         ("clusterStart", "clusterEnd", "peaks", "samples"))})}
+            for j, name in enumerate(("peaks", "bases", "sum", "max")):
+                entry[name] = cols[4 + j][cells].reshape(int(k[g]), int(m[g]))
+            result.append(entry)
+        return result
+
     def _coverage_stats(self, ranks, torch_device=None):
         """one peakseg_hip_problem_set_pack_coverage_stats: ranks int64 [n_contigs, k], k at most
         max_ranks -> (value int32 [n_contigs, k], moments uint64 [n_contigs, 6]); with torch_device
