@@ -544,6 +544,11 @@ int peakseg_hip_problem_set_packed_region_stats_download(psd_problem_set *set, i
 /* the tile of the fold: runs one workgroup folds for one region at a time, laid over the contig's
  * 16-byte aligned range as pack_segment_stats' tiles are (tests aim at its boundaries) */
 int peakseg_hip_region_stats_tile_runs(void);
+/* the workgroups of the fold launch of the calling thread's last pack_region_stats or
+ * pack_peak_clusters (0 before the first): eight per compute unit, or the call's upper bound on its
+ * (region, tile) items where that is smaller.  A workgroup takes the items blockIdx.x,
+ * blockIdx.x + grid, ...: tests size their work lists from it, read-only */
+long long peakseg_hip_region_stats_last_fold_grid(void);
 /* milliseconds (HIP events) of the calling thread's last pack_region_stats: the launches */
 int peakseg_hip_region_stats_last_ms(float *ms);
 

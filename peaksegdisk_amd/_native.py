@@ -251,6 +251,8 @@ def declare(lib):
     lib.peakseg_hip_problem_set_packed_region_stats_download.restype = c.c_int
     lib.peakseg_hip_region_stats_tile_runs.argtypes = []
     lib.peakseg_hip_region_stats_tile_runs.restype = c.c_int
+    lib.peakseg_hip_region_stats_last_fold_grid.argtypes = []
+    lib.peakseg_hip_region_stats_last_fold_grid.restype = c.c_longlong
     lib.peakseg_hip_region_stats_last_ms.argtypes = [c.POINTER(c.c_float)]
     lib.peakseg_hip_region_stats_last_ms.restype = c.c_int
     lib.peakseg_hip_problem_set_pack_peak_clusters.argtypes = [
@@ -311,6 +313,7 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_pack_region_stats",
     "peakseg_hip_problem_set_packed_region_stats_download",
     "peakseg_hip_region_stats_tile_runs", "peakseg_hip_region_stats_last_ms",
+    "peakseg_hip_region_stats_last_fold_grid",
     "peakseg_hip_problem_set_pack_peak_clusters",
     "peakseg_hip_problem_set_packed_peak_clusters_download",
     "peakseg_hip_peak_clusters_last_ms", "peakseg_hip_peak_clusters_probe",

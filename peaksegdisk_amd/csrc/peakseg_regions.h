@@ -6,6 +6,7 @@
 namespace {
 
 thread_local float g_regions_ms = 0.f;
+thread_local long long g_fold_grid = 0; /* workgroups of the calling thread's last fold launch */
 
 void region_error_text(int contig, long long index, long long rs, long long re, bool known) {
   if (known)
@@ -53,6 +54,7 @@ int regions_fold(psd_problem_set *s, RegionTable &t, long long n, const int *fla
   HIP_TRY(hipGetLastError());
   long long grid = 8ll * (s->n_cu > 0 ? s->n_cu : 256);
   if (most_items < grid) grid = most_items > 0 ? most_items : 1;
+  g_fold_grid = grid;
   hipLaunchKernelGGL(rg::fold_kernel, dim3((unsigned)grid), dim3(rg::THREADS), 0, s->stream, n,
                      (const int *)t.off, (const long long *)t.block_sum, (const rg::Span *)t.span,
                      (const int *)s->d.count, (const int *)s->d.weight, t.sum, t.mx);
@@ -259,6 +261,8 @@ extern "C" int peakseg_hip_problem_set_packed_region_stats_download(psd_problem_
 }
 
 extern "C" int peakseg_hip_region_stats_tile_runs(void) { return psd::regions::TILE; }
+
+extern "C" long long peakseg_hip_region_stats_last_fold_grid(void) { return g_fold_grid; }
 
 extern "C" int peakseg_hip_region_stats_last_ms(float *ms) {
   if (ms) *ms = g_regions_ms;

@@ -23,6 +23,7 @@ def test_symbols_and_status(psd):
     for name in ("peakseg_hip_problem_set_pack_region_stats",
                  "peakseg_hip_problem_set_packed_region_stats_download",
                  "peakseg_hip_region_stats_tile_runs", "peakseg_hip_region_stats_last_ms",
+                 "peakseg_hip_region_stats_last_fold_grid",
                  "peakseg_hip_problem_set_pack_peak_clusters",
                  "peakseg_hip_problem_set_packed_peak_clusters_download",
                  "peakseg_hip_peak_clusters_last_ms", "peakseg_hip_peak_clusters_probe"):
@@ -33,6 +34,7 @@ def test_symbols_and_status(psd):
     text = native.status_message(22, "f", "1", "d")
     assert text.startswith("error code 22") and "group" in text and "region" in text
     assert native.lib.peakseg_hip_region_stats_tile_runs() % 4 == 0
+    assert native.lib.peakseg_hip_region_stats_last_fold_grid() >= 0
     ms = ctypes.c_float(-1.0)
     assert native.lib.peakseg_hip_region_stats_last_ms(ctypes.byref(ms)) == 0 and ms.value >= 0.0
     assert native.lib.peakseg_hip_peak_clusters_last_ms(ctypes.byref(ms)) == 0 and ms.value >= 0.0
@@ -140,3 +142,57 @@ def test_cluster_reference_by_hand():
     assert table.shape == (0, 4) and m_peaks.shape == (0, 0)
     table, _ = cluster_ref([([1], [10]), ([2], [3]), ([9], [12]), ([12], [13])])   # nested, chained, abutting
     assert table.tolist() == [[1, 12, 3, 3], [12, 13, 1, 1]]
+
+
+def test_prefix_region_reference_equals_the_slices():
+    """region_ref_prefix() against region_ref(): the by-hand cases, and random regions of every
+    length (a base, a power of two, one more, the contig and beyond both ends) on vectors of 1, 2,
+    1000 and 4097 bases, with counts up to 2^31 - 1"""
+    from consensus_ref import region_ref_prefix
+    vector = [3, 3, 7, 7, 7, 1]
+    starts = [100, 101, 103, 90, 104, 106, 50, 99, 102]
+    ends = [106, 103, 104, 101, 200, 110, 60, 300, 103]
+    for got, want in zip(region_ref_prefix(vector, 100, starts, ends), region_ref(vector, 100, starts, ends)):
+        assert got.dtype == want.dtype and got.tolist() == want.tolist()
+    rng = np.random.default_rng(12)
+    for n, first in ((1, 0), (2, 5), (1000, 77), (4097, 2147483647 - 4097)):
+        v = rng.integers(0, 2147483648, n).astype(np.int32)
+        a = np.concatenate([rng.integers(first - 20, first + n + 10, 2999), [first - 3]])
+        width = np.concatenate([rng.integers(1, n + 40, 2000), 2 ** rng.integers(0, 13, 500),
+                                2 ** rng.integers(0, 13, 499) + rng.integers(-1, 2, 499), [n + 6]])
+        b = np.minimum(a + np.maximum(width, 1), 2 ** 31 - 1)
+        keep = a < b
+        got, want = region_ref_prefix(v, first, a[keep], b[keep]), region_ref(v, first, a[keep], b[keep])
+        for g, w in zip(got, want):
+            assert g.dtype == w.dtype and np.array_equal(g, w), (n, first)
+        assert (want[0] == 0).any() and (want[0] == n).any()
+    empty = region_ref_prefix([], 0, [0, 5], [3, 9])
+    assert [x.tolist() for x in empty] == [[0, 0]] * 3
+    assert [len(x) for x in region_ref_prefix(vector, 0, [], [])] == [0, 0, 0]
+
+
+def test_sorted_cluster_reference_equals_the_sweep():
+    """cluster_ref_sorted() against cluster_ref(): the by-hand cases and random members with
+    abutting, nested, chained and identical peaks"""
+    from consensus_ref import cluster_ref_sorted
+    cases = [[([10, 30, 60], [20, 40, 70]), ([20, 35, 90], [25, 62, 95]), ([], [])],
+             [([5], [9]), ([5], [9])], [], [([], []), ([], [])],
+             [([1], [10]), ([2], [3]), ([9], [12]), ([12], [13])],
+             [([10, 19], [19, 30]), ([19], [25])]]
+    rng = np.random.default_rng(13)
+    for n, top in ((40, 300), (300, 2000), (300, 20000)):
+        members = []
+        for _ in range(4):
+            cuts = np.sort(rng.choice(np.arange(top), size=2 * n, replace=False))
+            start, end = cuts[0::2].copy(), cuts[1::2].copy()
+            glue = rng.random(n - 1) < 0.2
+            end[:-1][glue] = start[1:][glue]
+            members.append((start, end))
+        members.append(members[0])
+        cases.append(members)
+    for members in cases:
+        table, m_peaks = cluster_ref_sorted(members)
+        want_table, want_peaks = cluster_ref(members)
+        assert table.dtype == want_table.dtype and table.shape == want_table.shape
+        assert np.array_equal(table, want_table) and np.array_equal(m_peaks, want_peaks)
+    assert len(cluster_ref(cases[-1])[0]) > 50

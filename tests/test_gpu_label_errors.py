@@ -234,7 +234,70 @@ def scenario_many_rows(psd, wrap):
         pset.close()
 
 
-# ---- scenario 5: refusals --------------------------------------------------------------------
+# ---- scenario 5: waves whose 64 lanes all count for one problem -------------------------------
+
+def full_wave_labels(ps, pe):
+    """3 x 64 labels around the peaks [ps[i], pe[i]) of a model (in genomic order, at least 20 bases
+    wide and 40 apart): 64 peakStart / peakEnd labels that hold two starts or two ends (false
+    positives that could also have been false negatives), 64 noPeaks labels over a peak, 64 labels
+    that find nothing (peaks between two peaks, peakStart and peakEnd inside one)"""
+    n = len(ps)
+    assert n >= 3 and np.all(pe - ps >= 20) and np.all(ps[1:] - pe[:-1] >= 40)
+    rows = []
+    for k in range(64):
+        i, a, b = k % (n - 1), 1 + k % 7, 1 + (k // 7) % 9
+        if k % 2:
+            rows.append((ps[i] - a, ps[i + 1] + b, PEAK_START))
+        else:
+            rows.append((pe[i] - a, pe[i + 1] + b, PEAK_END))
+    for k in range(64):
+        i, a = k % n, k % 13
+        rows.append([(ps[i] + a, ps[i] + a + 3), (ps[i] - 5, ps[i] + 1 + a), (pe[i] - 1, pe[i] + 30),
+                     (ps[0] - 9, pe[n - 1] + a)][k % 4] + (NO_PEAKS,))
+    for k in range(64):
+        i, a = k % (n - 1), k % 11
+        rows.append([(pe[i] + a, pe[i] + a + 20, PEAKS), (ps[i] + 1, ps[i] + 9 + a, PEAK_START),
+                     (ps[i], ps[i] + 10 + a, PEAK_END), (pe[i], pe[i] + 25 + a, PEAK_START)][k % 4])
+    cols = np.array(rows, dtype=np.int64)
+    return tuple(np.ascontiguousarray(cols[:, j], dtype=np.int32) for j in range(3))
+
+
+def scenario_full_waves(psd, wrap):
+    """count_kernel packs a wave's four sums into the bytes of one word: here the 64 lanes of a wave
+    all belong to one problem and all count, so a byte holds 64.  The second problem has the same
+    labels shuffled: its waves mix the three kinds."""
+    v = np.full(9000, 2, dtype=np.int32)
+    for j, a in enumerate(range(500, 8500, 1000)):
+        v[a:a + 300 + 20 * j] = 40 + 5 * j
+    first = 700
+    pset = psd.ProblemSet.from_dense([as_numpy(v), as_numpy(v)], [(0, 10.0), (1, 10.0)])
+    try:
+        pset.solve()
+        columns = pset.segment_columns(first_chromStart=[first, first])
+        ps, pe = (x[::-1] for x in peaks_of(columns[0]))
+        assert len(ps) == 8 and np.array_equal(ps, first + np.arange(500, 8500, 1000))
+        ordered = full_wave_labels(ps, pe)
+        order = np.random.default_rng(15).permutation(len(ordered[0]))
+        shuffled = tuple(np.ascontiguousarray(a[order]) for a in ordered)
+        # what the scenario is for did occur, from the yardstick's columns: packed rows 0-63, 64-127
+        # and 128-191 are waves of problem 0 whose lanes all count in the same bytes
+        _, fp, fn, totals = brute_force(columns[0], ordered)
+        codes = ordered[2]
+        possible_fp, possible_fn = codes != PEAKS, codes != NO_PEAKS
+        assert len(codes) == 192 and pset.problems[0][0] == 0
+        assert fp[:64].all() and possible_fp[:64].all() and possible_fn[:64].all() and not fn[:64].any()
+        assert fp[64:128].all() and possible_fp[64:128].all() and not possible_fn[64:128].any()
+        assert fn[128:].all() and possible_fn[128:].all() and not fp[128:].any()
+        assert totals == [192, 128, 64, 128 + int(np.sum(codes[128:] != PEAKS)), 128]
+        mixed = brute_force(columns[1], shuffled)
+        assert mixed[3] == totals and 0 < mixed[1][:64].sum() < 64
+        got, _, _ = check_set(pset, [ordered, shuffled], [first, first], wrap, "full waves")
+        assert got[0].tolist() == totals and got[1].tolist() == totals
+    finally:
+        pset.close()
+
+
+# ---- scenario 6: refusals --------------------------------------------------------------------
 
 BAD_CASES = [   # (labels of contig 1, what the text must hold)
     ("count", None, "contig 1"),
@@ -324,7 +387,7 @@ def scenario_refusals(psd, wrap, device_side):
         plain.close()
 
 
-# ---- scenario 6: the torch_device form (GPU only) --------------------------------------------
+# ---- scenario 7: the torch_device form (GPU only) --------------------------------------------
 
 def scenario_torch_device(psd, wrap):
     """the tensors alias the packed buffers and hold what the download returns"""
@@ -353,7 +416,7 @@ def scenario_torch_device(psd, wrap):
             assert np.array_equal(got[int(offs[k]):int(offs[k + 1])], want)
 
 
-# ---- scenario 7: PeakSegFPOP_dense(..., labels=...) ------------------------------------------
+# ---- scenario 8: PeakSegFPOP_dense(..., labels=...) ------------------------------------------
 
 def scenario_api(psd, wrap):
     dense = mono27ac_dense()
@@ -391,7 +454,8 @@ def scenario_api(psd, wrap):
     assert "false positive" in fits[0].label_errors["status"].tolist()
 
 
-SCENARIOS = [scenario_mono27ac, scenario_ties, scenario_shared, scenario_many_rows, scenario_api]
+SCENARIOS = [scenario_mono27ac, scenario_ties, scenario_shared, scenario_many_rows,
+             scenario_full_waves, scenario_api]
 
 
 # ---- MI355X ----------------------------------------------------------------------------------

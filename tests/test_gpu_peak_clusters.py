@@ -15,7 +15,7 @@ import os
 import numpy as np
 import pytest
 
-from consensus_ref import cluster_ref, region_ref
+from consensus_ref import cluster_ref, cluster_ref_sorted, region_ref
 from test_gpu_dense import as_cuda, as_numpy
 
 GPU = pytest.mark.gpu
@@ -56,9 +56,9 @@ def probe(members):
         m_peaks[:k * m].reshape(k, m).astype(np.int64)
 
 
-def check_probe(members, what):
+def check_probe(members, what, ref=cluster_ref):
     k, table, m_peaks = probe(members)
-    want_table, want_peaks = cluster_ref(members)
+    want_table, want_peaks = ref(members)
     assert k == len(want_table), (what, k, len(want_table), _lib().peakseg_hip_last_error().decode())
     assert np.array_equal(table, want_table), (what, table[:8].tolist(), want_table[:8].tolist())
     assert np.array_equal(m_peaks, want_peaks), what
@@ -127,6 +127,43 @@ def scenario_probe_random(psd, wrap):
     sparse = [random_peaks(rng, n, 0, 2000000) for n in (3000, 50, 1)]
     table, _ = check_probe(sparse, "sparse")
     assert np.sum(table[:, 3] == 1) >= 1000      # (the 50 wide peaks of the second member join the rest)
+
+
+def sparse_peaks(rng, n, hi, widest):
+    """n sorted disjoint peaks of 1 to `widest` bases scattered over [0, hi): a peak that would reach
+    into the next one ends where that begins"""
+    start = np.unique(rng.integers(0, hi - widest, n + n // 8))
+    assert len(start) >= n
+    start = np.sort(rng.choice(start, n, replace=False))
+    end = start + rng.integers(1, widest + 1, n)
+    end[:-1] = np.minimum(end[:-1], start[1:])
+    return start, end
+
+
+def scenario_probe_scan_top(psd, wrap):
+    """More than 2 x 65536 peaks in the members of one group (the probe takes one group per call;
+    two calls with different member counts): mark_kernel runs more than 256 workgroups, so a thread
+    of the top-level scan of the lead flags has several blocks, and a peak's cluster index hangs on
+    the prefix sums across the threads' shares."""
+    rng = np.random.default_rng(43)
+    for sizes in ((50000, 45000, 40300), (70000, 66000)):
+        n = sum(sizes)
+        n_blocks = (n + 1 + 255) // 256             # (an entry more than peaks: "all of them")
+        per = (n_blocks + 255) // 256
+        assert n > 2 * 65536 and n_blocks > 256 and per == 3 and n_blocks % per != 0, (n, n_blocks)
+        members = [sparse_peaks(rng, k, 60000000, 300) for k in sizes]
+        table, m_peaks = check_probe(members, "%d peaks" % n, cluster_ref_sorted)
+        # lead flags of both kinds in every block: a cluster per lead, fewer clusters than peaks,
+        # and in every stretch of 256 peaks of a member one that leads and one that does not
+        assert n // 2 < len(table) < n - n // 20, (n, len(table))
+        leads = np.concatenate([np.isin(ps, table[:, 0]) for ps, _ in members])
+        by_block = np.add.reduceat(leads.astype(np.int64), np.arange(0, n, 256))
+        assert by_block[:-1].min() > 0 and by_block[:-1].max() < 256
+        assert table[:, 2].max() >= 3 and (m_peaks == 0).any() and (table[:, 3] == len(sizes)).any()
+    # the yardstick of this size against the sweep, on a part cluster_ref() can afford
+    part = [(ps[:700], pe[:700]) for ps, pe in members]
+    for x, y in zip(cluster_ref_sorted(part), cluster_ref(part)):
+        assert np.array_equal(x, y)
 
 
 def scenario_probe_refusals(psd, wrap):
@@ -357,7 +394,7 @@ def scenario_api(psd, wrap):
 
 
 PROBE_SCENARIOS = [scenario_probe_small, scenario_probe_wide, scenario_probe_random,
-                   scenario_probe_refusals]
+                   scenario_probe_scan_top, scenario_probe_refusals]
 SET_SCENARIOS = [scenario_sets, scenario_set_refusals, scenario_api]
 SCENARIOS = PROBE_SCENARIOS + SET_SCENARIOS
 

@@ -11,6 +11,7 @@ criterion and the validation figures in numpy float64 from the weights a call re
 objective is convex, so a subgradient of sup-norm <= threshold at the returned weights certifies them
 without comparing against another solver's path.  Inputs come from synthetic.uniform01 (Box-Muller
 where normals are wanted): the same on every machine."""
+import contextlib
 import math
 
 import numpy as np
@@ -39,8 +40,23 @@ def _lib():
 
 
 def names(p):
+    """the package's 36 feature names, and beyond them names of this file's own"""
     from peaksegdisk_amd.grid import FEATURE_NAMES
-    return list(FEATURE_NAMES[:p])
+    return list(FEATURE_NAMES[:p]) + ["wide.%d" % k for k in range(len(FEATURE_NAMES), p)]
+
+
+@contextlib.contextmanager
+def known_names(p):
+    """The Python layer takes no column it does not know, and it knows 36; the kernel takes 64.  For
+    the fits that are as wide as the kernel, grid.FEATURE_NAMES holds names(p) while they are made,
+    so that they go through fit_penalty_model like every other."""
+    from peaksegdisk_amd import grid
+    kept = grid.FEATURE_NAMES
+    grid.FEATURE_NAMES = tuple(names(max(p, len(kept))))
+    try:
+        yield
+    finally:
+        grid.FEATURE_NAMES = kept
 
 
 # ---- inputs -----------------------------------------------------------------------------------
@@ -89,6 +105,9 @@ SHAPES = {                       # (n, p, F, regularizations)
     "65x36": (65, 36, 5, [0.02, 0.05, 0.2, 5.0]),
     "257x5": (257, 5, 3, [0.01, 0.05, 0.2, 5.0]),
     "1000x12": (1000, 12, 16, [0.01, 0.1, 1.0]),
+    # as wide as the kernel: every lane of wave 0 has a weight, the intercept is slot 64; one less
+    "300x64": (300, 64, 5, [0.02, 0.05, 0.2, 5.0]),
+    "301x63": (301, 63, 5, [0.02, 0.05, 0.2, 5.0]),
 }
 _FITS = {}
 
@@ -100,8 +119,9 @@ def fitted(psd, key):
         n, p, folds, reg = SHAPES[key]
         frame = raw_features(n, p, 100 + n)
         targets = targets_for(frame, 200 + n)
-        fit = psd.fit_penalty_model(frame, targets, regularizations=reg, n_folds=folds,
-                                    threshold=THRESHOLD)
+        with known_names(p):
+            fit = psd.fit_penalty_model(frame, targets, regularizations=reg, n_folds=folds,
+                                        threshold=THRESHOLD)
         _FITS[at] = (frame, targets, fit)
     return _FITS[at]
 
@@ -228,8 +248,9 @@ def scenario_certificate(psd):
         if p == 36:       # log(log(v)) of a v <= 1
             assert set(fit.dropped_features.values()) == {"not finite"}
             assert 20 <= len(fit.feature_names) < 36
-        else:
+        else:       # the width reaches the kernel
             assert fit.feature_names == names(p) and fit.dropped_features == {}
+            assert len(fit.feature_names) == p and fit.weights.shape[2] == p + 1
         lo, hi = targets[:, 0], targets[:, 1]
         assert np.all(np.isinf(lo[0::3])) and np.all(np.isinf(hi[1::3])) and np.all(np.isfinite(targets[2::3]))
         check_certificate(frame, targets, fit, key)
@@ -241,9 +262,10 @@ def scenario_certificate(psd):
 def scenario_objective(psd):
     """F_dev - F_ref <= threshold (|w_dev - w_ref|_1 + |b_dev - b_ref|) + 1e-9: the first-order bound
     of a convex function whose subgradient at w_dev has sup-norm at most threshold"""
-    for key in ("63x3", "257x5"):
+    for key in ("63x3", "257x5", "300x64"):
         frame, targets, fit = fitted(psd, key)
         x = standardised(frame, fit)
+        assert x.shape[1] == SHAPES[key][1]
         lo, hi = targets[fit.rows, 0], targets[fit.rows, 1]
         lam = ref.gram_lambda_max(x)
         for s in range(fit.weights.shape[0]):
@@ -432,6 +454,9 @@ def scenario_arguments(psd):
         psd.fit_penalty_model(frame, targets, regularizations=[0.1, 0.2], n_folds=1)
     with pytest.raises(ValueError):
         psd.fit_penalty_model(frame, targets, n_folds=17)
+    with known_names(65):           # one column more than the kernel takes
+        with pytest.raises(ValueError, match="65 features; at most 64"):
+            psd.fit_penalty_model(raw_features(n, 65, 5), targets)
     # rows that say nothing and columns that are not finite or constant: dropped and reported
     wide = raw_features(n, 4, 5)
     wide.iloc[3, 2] = np.nan

@@ -182,6 +182,62 @@ def scenario_three_contigs(wrap):
                  "no reads")
 
 
+LONG_TILES = 3 * 256        # of the long contig: the scan of the tile sums takes 4 tiles per thread
+
+
+def long_contig_reads(weighted):
+    """(contigs, extents) of scenario_long_contig: a contig of LONG_TILES tiles and half a tile more
+    and a short one behind it.  The long one has 30000 short reads (reads_around: one across every
+    tile border), 20 reads that each span hundreds of tiles, and single-base reads on the last base
+    in front of a tile wherever the coverage there would equal that in front of the tile before."""
+    T = _lib().peakseg_hip_dense_tile_bases()
+    rng = np.random.default_rng(20250302)
+    lo = 5000
+    hi = lo + LONG_TILES * T + T // 2 + 1
+    s, e, k = reads_around(rng, lo, hi, 30000, T)
+    first = rng.integers(lo - 50, lo + 200 * T, 20)
+    first[0] = lo + T // 3                                   # from the first tile to the last
+    last = np.minimum(first + rng.integers(150 * T, 600 * T, 20), hi + 77)
+    last[0] = hi - 9
+    s = np.concatenate([s, first.astype(np.int32)])
+    e = np.concatenate([e, last.astype(np.int32)])
+    k = np.concatenate([k, rng.integers(1, 9, 20).astype(np.int32)])
+    cov = numpy_pileup(s, e, k if weighted else None, lo, hi)
+    n_tiles = -(-(hi - lo) // T)
+    carry = cov[T - 1::T][:n_tiles - 1].astype(np.int64)     # in front of tiles 1, 2, ...
+    more = []
+    for t in range(1, len(carry)):                           # (carry[t - 1] is final when t is reached)
+        if carry[t] == carry[t - 1]:
+            carry[t] += 1
+            more.append(lo + (t + 1) * T - 1)
+    more = np.array(more, dtype=np.int32)
+    s, e = np.concatenate([s, more]), np.concatenate([e, more + 1])
+    k = np.concatenate([k, np.ones(len(more), np.int32)])
+    order = rng.permutation(len(s))
+    long_one = (s[order], e[order], k[order]) if weighted else (s[order], e[order])
+    short_extent = (300, 300 + T + 5)
+    short_one = reads_around(rng, short_extent[0], short_extent[1], 300, T)
+    return [long_one, short_one if weighted else short_one[:2]], [(lo, hi), short_extent]
+
+
+def scenario_long_contig(wrap):
+    """A contig of more than 256 tiles: a thread of tile_scan_kernel takes a share of several tiles
+    and walks it twice, and the carry it writes must advance from tile to tile.  Every read counting
+    1, and count as weights."""
+    T = _lib().peakseg_hip_dense_tile_bases()
+    for weighted in (False, True):
+        contigs, extents = long_contig_reads(weighted)
+        want = check_pileup(contigs, extents, "each", wrap, ("long contig", weighted))
+        # what the scenario is for did occur, from the numpy pile-up: a share of several tiles, and
+        # in front of every tile a coverage that is not zero and not that of the tile before
+        n_tiles = -(-len(want[0]) // T)
+        assert n_tiles > 256 and -(-n_tiles // 256) >= 2, n_tiles
+        carry = want[0][T - 1::T][:n_tiles - 1].astype(np.int64)
+        assert len(carry) == n_tiles - 1 and carry.min() > 0 and np.all(np.diff(carry) != 0)
+        assert len(set(carry.tolist())) > 8
+        assert len(want[1]) == T + 5 and want[1].any()       # (its first tile is not the call's first)
+
+
 def scenario_one_address(wrap):
     """5000 identical reads and 5000 reads of length 1 at one base: many adds to one address"""
     s = np.concatenate([np.full(5000, 300), np.full(5000, 350)]).astype(np.int32)
@@ -484,6 +540,7 @@ def child_main(which, tmp):
         scenario_pileup(as_cuda)
         scenario_three_contigs(as_cuda)
         scenario_one_address(as_cuda)
+        scenario_long_contig(as_cuda)
         scenario_device_offsets(as_cuda)
         scenario_refusals(as_cuda)
         scenario_python_refusals(psd, as_cuda)
@@ -499,6 +556,12 @@ def test_gpu_reads_pileup_numpy(psd):
     scenario_pileup(as_numpy)
     scenario_three_contigs(as_numpy)
     scenario_one_address(as_numpy)
+    print("pile-up of the last call: scatter %.3f ms, scans %.3f ms" % pileup_ms())
+
+
+@GPU
+def test_gpu_reads_long_contig_numpy(psd):
+    scenario_long_contig(as_numpy)
     print("pile-up of the last call: scatter %.3f ms, scans %.3f ms" % pileup_ms())
 
 

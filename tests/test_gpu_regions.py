@@ -9,7 +9,9 @@ torch first, as tests/test_gpu_dense.py does).
 The yardstick is consensus_ref.region_ref(): a slice of the per-base vector.  Integer arithmetic, so
 the comparisons are for equality.  The contigs have at most three tiles of runs and are built run by
 run, so that the regions can aim at run ends, at the tiles' boundaries and at the threshold between
-the regions a thread finishes alone and those that go through the fold."""
+the regions a thread finishes alone and those that go through the fold.  Two scenarios leave the
+sizes at which every loop makes one trip: more work items than three times the fold's grid (read
+from the library, not assumed), and more than 65536 regions through the top-level scan."""
 import ctypes
 import os
 import subprocess
@@ -17,7 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from consensus_ref import region_ref
+from consensus_ref import region_ref, region_ref_prefix
 from test_gpu_dense import as_cuda, as_numpy, rle
 
 GPU = pytest.mark.gpu
@@ -136,12 +138,12 @@ def wrap_regions(regions, wrap):
     return [None if e is None else tuple(wrap(a) for a in e) for e in regions]
 
 
-def check_regions(pset, contigs, regions, firsts, wrap, what=""):
+def check_regions(pset, contigs, regions, firsts, wrap, what="", ref=region_ref):
     got = pset.region_stats(wrap_regions(regions, wrap), first_chromStart=firsts)
     assert len(got) == len(contigs)
     for c, (entry, (_, _, vector)) in enumerate(zip(regions, contigs)):
         starts, ends = entry if entry is not None else (np.zeros(0, np.int32),) * 2
-        want = region_ref(vector, 0 if firsts is None else firsts[c], starts, ends)
+        want = ref(vector, 0 if firsts is None else firsts[c], starts, ends)
         for name, w, dt in zip(("bases", "sum", "max"), want, (np.int32, np.int64, np.int32)):
             g = got[c][name]
             assert g.dtype == dt and len(g) == len(starts), (what, c, name)
@@ -221,10 +223,200 @@ def scenario_many_small(psd, wrap):
         pset.close()
 
 
-SCENARIOS = [scenario_aimed, scenario_many_small]
+# ---- scenarios 3 and 4: past one trip of the fold, past one trip of the top-level scan -------
+
+SMALL = 16      # region_stats.h: a region of at most this many runs is its thread's alone
 
 
-# ---- scenario 3: refusals --------------------------------------------------------------------
+def fold_grid():
+    return int(_lib().peakseg_hip_region_stats_last_fold_grid())
+
+
+def region_tiles(weight, first, run_offset, starts, ends):
+    """the (region, tile) items of every region of one contig, by the header's formula: j0 the first
+    run that ends after a, j1 the first that ends at or after b; at most SMALL runs: none; else the
+    tiles of the contig's 16-byte aligned range that the whole runs j0 + 1 .. j1 - 1 meet"""
+    tile = tile_runs()
+    run_end = np.cumsum(weight)
+    a = np.maximum(np.asarray(starts, np.int64) - first, 0)
+    b = np.minimum(np.asarray(ends, np.int64) - first, int(run_end[-1]))
+    j0 = np.searchsorted(run_end, a, side="right")
+    j1 = np.minimum(np.searchsorted(run_end, b, side="left"), len(run_end) - 1)
+    lead = run_offset % 4
+    tiles = (j1 - 1 + lead) // tile - (j0 + 1 + lead) // tile + 1
+    return np.where((b > a) & (j1 - j0 >= SMALL), tiles, 0).astype(np.int64)
+
+
+def run_regions(weight, first, j0, j1):
+    """the regions that are exactly the runs j0[i] .. j1[i] of a contig"""
+    end = np.cumsum(weight)
+    return first + (end - weight)[j0], first + end[j1]
+
+
+def long_regions(rng, n_runs, n):
+    """n spans of more than SMALL runs: a third within a tile's worth, the rest of any length"""
+    tile = tile_runs()
+    length = np.where(rng.random(n) < 0.33, rng.integers(SMALL + 1, tile // 2, n),
+                      rng.integers(SMALL + 1, n_runs, n))
+    j0 = (rng.random(n) * (n_runs - length)).astype(np.int64)
+    return j0, j0 + length - 1
+
+
+def two_contigs():
+    """contigs 0 and 2 of make_contigs(): three tiles of runs, and two and a half tiles at run offset
+    3 modulo 4; -> (contigs, offsets, the indices of the two)"""
+    contigs, offsets = make_contigs()
+    assert offsets[0] % 4 == 0 and offsets[2] % 4 == 3
+    return contigs, offsets, (0, 2)
+
+
+def packed(regions):
+    """the regions of a call in the order of the packed columns: contig after contig"""
+    return [r for r in regions if r is not None]
+
+
+def scenario_fold_trips(psd, wrap):
+    """More (region, tile) items than three times the fold's grid, and no multiple of it: every
+    workgroup makes three or four trips through its loop, the last of them partial, and a region's
+    tiles go to workgroups in different trips."""
+    contigs, offsets, use = two_contigs()
+    pset = psd.ProblemSet.from_dense([as_numpy(c[2]) for c in contigs], [(0, 5.0)])
+    try:
+        # the grid of this device: a call whose bound on the items (regions x tiles of the contig,
+        # 16384 x 3) is far above eight workgroups per compute unit, so that the grid is the device's
+        count, weight, _ = contigs[0]
+        at = np.arange(16384) % len(count)
+        dry = [None] * len(contigs)
+        dry[0] = tuple(as_numpy(x) for x in run_regions(weight, FIRSTS[0], at, at))
+        check_regions(pset, contigs, dry, FIRSTS, wrap, "dry", region_ref_prefix)
+        grid = fold_grid()
+        assert 0 < grid < 16384 and grid % 8 == 0, grid
+        rng = np.random.default_rng(77)
+        want_items = 3 * grid + grid // 3 + 1
+        rows = {c: [] for c in use}
+        for c in use:
+            count, weight, _ = contigs[c]
+            n, first, bases = len(count), FIRSTS[c], int(weight.sum())
+            j0, j1 = long_regions(rng, n, want_items // 6)
+            s, e = run_regions(weight, first, j0, j1)
+            cut = rng.integers(0, 2, (2, len(s)))                       # some edges cut a run
+            s = s + cut[0] * (weight[j0] > 1)
+            e = e - cut[1] * (weight[j1] > 1)
+            rows[c] += list(zip(s.tolist(), e.tolist()))
+            k0 = rng.integers(0, n - 3, len(s) // 3)                    # small ones between them
+            s, e = run_regions(weight, first, k0, k0 + rng.integers(0, 3, len(k0)))
+            rows[c] += list(zip(s.tolist(), e.tolist()))
+            for _ in range(len(k0) // 2):                               # ... and regions of no base
+                a = int(rng.integers(1, 500))
+                rows[c].append((first - a - 40, first - a) if a % 2 else
+                               (first + bases + a, first + bases + a + 40))
+            rows[c] += [rows[c][int(i)] for i in rng.integers(0, want_items // 6, 120)]   # repeated
+        # top up with regions of one item each until the count is what was aimed at
+        def build():
+            out = [None] * len(contigs)
+            for c in use:
+                cols = np.array(rows[c], dtype=np.int64)
+                order = np.random.default_rng(5 + c).permutation(len(cols))
+                out[c] = (as_numpy(cols[order, 0]), as_numpy(cols[order, 1]))
+            return out
+
+        def items_of(regions):
+            return [region_tiles(contigs[c][1], FIRSTS[c], offsets[c], *regions[c]) for c in use]
+        regions = build()
+        items = int(sum(t.sum() for t in items_of(regions)))
+        assert items < want_items, (items, want_items)
+        count, weight, _ = contigs[2]
+        for k in range(want_items - items):
+            j0 = 40 + 7 * (k % 100)
+            s, e = run_regions(weight, FIRSTS[2], np.array([j0]), np.array([j0 + SMALL + 3 + k % 50]))
+            rows[2].append((int(s[0]), int(e[0])))
+        regions = build()
+        tiles = np.concatenate(items_of(regions))
+        items = int(tiles.sum())
+        # what the scenario is for did occur, from its own inputs
+        print("fold grid", grid, "items", items, "regions", len(tiles))
+        assert items >= 3 * grid and items % grid != 0, (items, grid)
+        assert np.sum(tiles == 1) > 100 and np.sum(tiles == 2) > 100 and np.sum(tiles == 3) > 100
+        blocks = [tiles[k:k + 256] for k in range(0, len(tiles), 256)]
+        gaps = 0
+        for block in blocks:                        # off[]: zeros between non-zero entries of a block
+            nz = np.flatnonzero(block)
+            gaps += len(nz) > 1 and int(np.sum(block[nz[0]:nz[-1]] == 0)) > 0
+        assert gaps == len(blocks), (gaps, len(blocks))
+        item0 = np.cumsum(tiles) - tiles            # a region's first item; its trip: item // grid
+        flat = np.concatenate([np.stack([np.full(len(r[0]), c), r[0], r[1]], axis=1)
+                               for c, r in enumerate(regions) if r is not None])
+        _, inverse = np.unique(flat, axis=0, return_inverse=True)
+        inverse = inverse.reshape(-1)
+        other_trip = 0
+        for k in np.flatnonzero(np.bincount(inverse) > 1):
+            same = np.flatnonzero((inverse == k) & (tiles > 0))
+            other_trip += len(set((item0[same] // grid).tolist())) > 1
+        assert other_trip >= 20, other_trip         # equal regions whose items differ in their trip
+        got = check_regions(pset, contigs, regions, FIRSTS, wrap, "fold trips")
+        assert fold_grid() == grid
+        assert np.sum(got[0]["bases"] == 0) > 50 and np.sum(got[2]["max"] == 1000000) > 50
+    finally:
+        pset.close()
+
+
+N_SCAN_TOP = 773 * 256 + 57     # more than 3 x 65536 + 1000: 774 blocks, 4 to a thread, the last 2
+
+
+def scenario_scan_top(psd, wrap):
+    """More than 65536 regions, so that a thread of the top-level scan has several blocks: windows of
+    one to three runs, and a few hundred long regions, whose work items hang on the prefix sums
+    across the threads' shares and within them."""
+    contigs, offsets, use = two_contigs()
+    n = N_SCAN_TOP
+    n_blocks = (n + 255) // 256
+    per = (n_blocks + 255) // 256
+    assert n >= 3 * 65536 + 1000 and n_blocks > 256 and per == 4 and n_blocks % per != 0
+    rng = np.random.default_rng(78)
+    n_first = n // 2 + 31                                   # contig 0's regions come first
+    contig_of = np.where(np.arange(n) < n_first, use[0], use[1])
+    is_long = np.zeros(n, bool)
+    is_long[rng.choice(n, 300, replace=False)] = True
+    forced = [5, n - 3, 8 * 256 + 7, 9 * 256 + 100]         # first block, last block, two blocks of thread 2
+    assert forced[2] // 256 // per == forced[3] // 256 // per and forced[3] // 256 == forced[2] // 256 + 1
+    is_long[forced] = True
+    regions = [None] * len(contigs)
+    tiles = []
+    for c in use:
+        count, weight, _ = contigs[c]
+        mine = np.flatnonzero(contig_of == c)
+        j0 = rng.integers(0, len(count) - 3, len(mine))
+        j1 = j0 + rng.integers(0, 3, len(mine))
+        lj0, lj1 = long_regions(rng, len(count), len(mine))
+        far = is_long[mine]
+        j0, j1 = np.where(far, lj0, j0), np.where(far, lj1, j1)
+        s, e = run_regions(weight, FIRSTS[c], j0, j1)
+        regions[c] = (as_numpy(s), as_numpy(e))
+        tiles.append(region_tiles(weight, FIRSTS[c], offsets[c], s, e))
+    tiles = np.concatenate(tiles)
+    # what the scenario is for did occur
+    assert len(tiles) == n and np.all(tiles[forced] > 0) and np.sum(tiles > 0) >= 300
+    assert np.sum(tiles == 0) > n - 400
+    by_block = np.add.reduceat(tiles, np.arange(0, n, 256))
+    assert len(by_block) == n_blocks > 256 and np.sum(by_block > 0) > 100 and np.sum(by_block == 0) > 100
+    share = np.add.reduceat(by_block, np.arange(0, n_blocks, per))
+    assert np.sum(share > 0) > 50 and share[-1] > 0 and len(share) < 256
+    pset = psd.ProblemSet.from_dense([as_numpy(c[2]) for c in contigs], [(0, 5.0)])
+    try:
+        check_regions(pset, contigs, regions, FIRSTS, wrap, "scan top", region_ref_prefix)
+    finally:
+        pset.close()
+    for c in use:                                           # the yardstick of this size against the slices
+        pick = rng.choice(len(regions[c][0]), 2000, replace=False)
+        s, e = regions[c][0][pick], regions[c][1][pick]
+        for x, y in zip(region_ref_prefix(contigs[c][2], FIRSTS[c], s, e), region_ref(contigs[c][2], FIRSTS[c], s, e)):
+            assert np.array_equal(x, y)
+
+
+SCENARIOS = [scenario_aimed, scenario_many_small, scenario_fold_trips, scenario_scan_top]
+
+
+# ---- scenario 5: refusals --------------------------------------------------------------------
 
 def raw_pack(pset, n_regions, arrays, on_device):
     """the C entry as it is: arrays[c] = two addresses; -> its return value"""
@@ -303,7 +495,7 @@ def scenario_refusals(psd, wrap, device_side):
         plain.close()
 
 
-# ---- scenario 4: the torch_device form (GPU only) --------------------------------------------
+# ---- scenario 6: the torch_device form (GPU only) --------------------------------------------
 
 def scenario_torch_device(psd, wrap):
     """the tensors alias the packed buffers and hold what the download returns"""

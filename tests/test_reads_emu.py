@@ -45,6 +45,10 @@ def test_emu_reads_many_adds_to_one_address(psd):
     gr.scenario_one_address(gr.as_numpy)
 
 
+def test_emu_reads_contig_of_more_than_256_tiles(psd):
+    gr.scenario_long_contig(gr.as_numpy)
+
+
 def test_emu_reads_refusals(psd):
     gr.scenario_refusals(gr.as_numpy)
 
