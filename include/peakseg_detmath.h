@@ -14,7 +14,10 @@
  *   - round-to-nearest-even mode, subnormals honoured (both true by default on x86-64
  *     and for f64 on gfx950).
  *
- * Accuracy (measured by tests/test_detmath.py against mpmath): < 1 ulp for both.
+ * Accuracy (measured by tests/test_detmath.py against mpmath): < 1 ulp for both; the largest
+ * errors found are 0.58 ulp for exp (at -709.77, a subnormal result, in units of 2^-1074) and
+ * 0.52 ulp for log, on the arguments that sit on the edges of the tables and of the range
+ * (tests/detmath_points.py).
  * Table-driven (128-entry tables, tools/gen_detmath_tables.py) with short polynomials: the
  * kernels are bound by the length of one wave's dependent instruction stream, and this form
  * needs about half the instructions of a table-free one and no division inside log.
@@ -78,14 +81,31 @@ PSD_HD static inline double psd_u2d(uint64_t u) {
  * against a constant piece) are repaired, exactly: the residual
  * a - q b of the hardware's q (one fma, exact), the neighbour of q on the side the residual
  * points to, its residual, and the quotient with the smaller one.  (A quotient of two doubles
- * is never exactly a midpoint: no tie; zero, infinite and NaN quotients fail both comparisons
- * and stay.)  Twelve instructions -- at every division of the kernel they cost 13 % -- so the
+ * is never exactly a midpoint: no tie; zero and NaN quotients and the infinite ones of x/0 and
+ * inf/x fail both comparisons and stay.)  That holds for NORMAL quotients, and they are the
+ * contract of psd_div.  Two kinds of quotient are outside it:
+ *   - One that OVERFLOWS: the residual of q = +-inf is infinite, the neighbour +-DBL_MAX has a
+ *     finite one and wins, so the device's psd_div returns +-DBL_MAX where the host's a / b is
+ *     +-inf.  Keeping q there takes one select; placed on the final comparison or on the
+ *     neighbour, it put the benchmark's median below the parent's three runs both times
+ *     (profiles/r19), and these divisions sit on the data point's dependent chain.  The solver
+ *     cannot produce such a quotient: every divisor is a piece's Linear coefficient, a sum of
+ *     weights normalised by a total below 2^48 -- zero (x/0: stays) or at least 2^-48 -- and the
+ *     numerators are Log coefficients and cost differences of data whose counts are below 2^31,
+ *     hundreds of binades from 2^976.
+ *   - A SUBNORMAL one: the residual is itself rounded there and a neighbour of the IEEE quotient
+ *     is not always restored; a correct quotient still stays (tests/test_detmath_forms_cpu.py),
+ *     and the device's own sequence was right on all of 92,156 such quotients
+ *     (tests/test_gpu_detmath.py).
+ * Twelve instructions -- at every division of the kernel they cost 13 % -- so the
  * other divisors keep the hardware's sequence: sums of bin widths (a whole number b < 2^48
  * keeps the quotient 1/(2b) of a unit away from every midpoint), and the iterates and slopes of
  * the Newton loops and the coefficients of DIFFERENCES of pieces, arbitrary reals that are
  * within 2^9 units below a power of two once in 2^44 times and then still need the numerator
  * to match. */
-/* q: a quotient of a by b that is at most one unit off; returns the correctly rounded one
+/* q: a quotient of a by b that is at most one unit off; returns the correctly rounded one where
+ * that is a normal number; q itself where q is zero or NaN or the infinity of x/0 or inf/x;
+ * +-DBL_MAX for the +-inf of an overflow
  * (host and device: tests/test_oracle_golden.py feeds it the IEEE quotient's neighbours) */
 PSD_HD static inline double psd_div_repair(double q, double a, double b) {
   const double e = psd_fma(-q, b, a);

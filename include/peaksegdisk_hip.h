@@ -727,6 +727,17 @@ int peakseg_hip_problem_set_profile(psd_problem_set *set, int problem, long long
  * sequence, which psd_div repairs; tests compare with the host build. */
 int peakseg_hip_math_probe(int op, int n, const double *x, double *y);
 
+/* Tests: one form of include/peakseg_detmath_core.h on the device, element by element, with one set
+ * of constants.  form: 0 psd_exp, 1 psd_log, 2 psd_exp2, 3 psd_log2, 4 psd_exp2_log, 5 psd_exp_nb,
+ * 6 psd_log_nb, 7 psd_log_wild_nb; set: 0 the plain constants (throughput and packed builds), 1 the
+ * constants in vector registers (latency build).  x0, x1, z: n arguments each (x1 for the forms of
+ * two exp / two log, z the log's argument of psd_exp2_log; NULL where the form reads none: zeros);
+ * y0, y1, lz: n results each (zeros where the form has none), rare: the record of the _nb forms,
+ * 0 before every element's call (0 for the other forms); any output may be NULL.  Returns 0,
+ * ERROR_NO_HIP_DEVICE, or -1 for a form, a set or an n out of range, before anything is launched. */
+int peakseg_hip_math_forms_probe(int form, int set, int n, const double *x0, const double *x1,
+                                 const double *z, double *y0, double *y1, double *lz, int *rare);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,34 @@ void oracle_log_vec(int n, const double *x, double *y) {
 void oracle_div_repair_vec(int n, const double *x, double *y) {
   for (int i = 0; i < n; i++) y[i] = psd_div_repair(x[i], x[n + i], x[2 * n + i]);
 }
+/* The host's side of peakseg_hip_math_forms_probe (include/peaksegdisk_hip.h): form 0 psd_exp,
+ * 1 psd_log, 2 psd_exp2, 3 psd_log2, 4 psd_exp2_log, 5 psd_exp_nb, 6 psd_log_nb, 7 psd_log_wild_nb
+ * of include/peakseg_detmath_core.h on n elements, with the plain functions every host program
+ * uses.  Results a form does not have are 0; rare[i] is 0 before element i's call.  Returns -1
+ * for a form out of range. */
+int oracle_math_form_vec(int form, int n, const double *x0, const double *x1, const double *z,
+                         double *y0, double *y1, double *lz, int *rare) {
+  if (form < 0 || form > 7) return -1;
+  for (int i = 0; i < n; i++) {
+    double r0 = 0.0, r1 = 0.0, rz = 0.0;
+    int rec = 0;
+    switch (form) {
+      case 0: r0 = psd_exp(x0[i]); break;
+      case 1: r0 = psd_log(x0[i]); break;
+      case 2: psd_exp2(x0[i], x1[i], &r0, &r1); break;
+      case 3: psd_log2(x0[i], x1[i], &r0, &r1); break;
+      case 4: psd_exp2_log(x0[i], x1[i], z[i], &r0, &r1, &rz); break;
+      case 5: r0 = psd_exp_nb(x0[i], &rec); break;
+      case 6: r0 = psd_log_nb(x0[i], &rec); break;
+      default: r0 = psd_log_wild_nb(x0[i], &rec); break;
+    }
+    y0[i] = r0;
+    y1[i] = r1;
+    lz[i] = rz;
+    rare[i] = rec;
+  }
+  return 0;
+}
 #endif
 
 /* ref: funPieceListLog.h:11-34 */

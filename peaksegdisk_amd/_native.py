@@ -104,6 +104,8 @@ def declare(lib):
     lib.peakseg_hip_problem_set_profile.restype = c.c_int
     lib.peakseg_hip_math_probe.argtypes = [c.c_int, c.c_int, c.c_void_p, c.c_void_p]
     lib.peakseg_hip_math_probe.restype = c.c_int
+    lib.peakseg_hip_math_forms_probe.argtypes = [c.c_int] * 3 + [c.c_void_p] * 7
+    lib.peakseg_hip_math_forms_probe.restype = c.c_int
     lib.PeakSegFPOP_dir_batch.argtypes = [
         c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_char_p), c.POINTER(c.c_int),
         c.POINTER(c.c_int)]
@@ -280,6 +282,7 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_result", "peakseg_hip_problem_set_segments",
     "peakseg_hip_problem_set_export_db", "peakseg_hip_problem_set_bytes",
     "peakseg_hip_problem_set_destroy", "peakseg_hip_math_probe", "peakseg_hip_parse_probe",
+    "peakseg_hip_math_forms_probe",
     "peakseg_hip_problem_set_profile", "peakseg_hip_problem_set_kernel_build",
     "PeakSegFPOP_dir_batch", "PeakSegFPOP_sequential_search",
     "PeakSegFPOP_sequential_search_batch",

@@ -92,6 +92,8 @@
 #include "region_stats.h"
 /* the clusters of overlapping peaks over the members of a group, and the cluster-by-member matrix */
 #include "peak_clusters.h"
+/* tests only: every form of the deterministic exp / log, element by element */
+#include "math_forms_probe.h"
 
 #include <ctype.h>
 #include <errno.h>
@@ -421,6 +423,48 @@ extern "C" int peakseg_hip_math_probe(int op, int n, const double *x, double *y)
   HIP_TRY(hipMemcpy(y, dy, (size_t)n * 8, hipMemcpyDeviceToHost));
   (void)hipFree(dx);
   (void)hipFree(dy);
+  return 0;
+}
+
+extern "C" int peakseg_hip_math_forms_probe(int form, int set, int n, const double *x0,
+                                            const double *x1, const double *z, double *y0,
+                                            double *y1, double *lz, int *rare) {
+  if (peakseg_hip_device_count() <= 0) {
+    set_error("no HIP device visible (this library has no CPU fallback)");
+    return ERROR_NO_HIP_DEVICE;
+  }
+  if (form < 0 || form >= psd::forms_probe::N_FORMS || set < 0 || set >= psd::forms_probe::N_SETS ||
+      n < 0) {
+    set_error("math forms probe: form %d, set %d or n %d out of range", form, set, n);
+    return -1;
+  }
+  if (n == 0) return 0;
+  /* three inputs, three outputs and the records: n elements each; an input the caller leaves out
+   * (NULL: the form does not read it) is zeros */
+  const size_t bytes = (size_t)n * 8;
+  double *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int *d_rare = nullptr;
+  for (auto &q : d) {
+    HIP_TRY(hipMalloc(&q, bytes));
+    HIP_TRY(hipMemset(q, 0, bytes));
+  }
+  HIP_TRY(hipMalloc(&d_rare, (size_t)n * 4));
+  HIP_TRY(hipMemset(d_rare, 0, (size_t)n * 4));
+  const double *in[3] = {x0, x1, z};
+  for (int k = 0; k < 3; k++)
+    if (in[k]) HIP_TRY(hipMemcpy(d[k], in[k], bytes, hipMemcpyHostToDevice));
+  const unsigned blocks = ((unsigned)n + psd::forms_probe::THREADS - 1u) / psd::forms_probe::THREADS;
+  hipLaunchKernelGGL(psd::forms_probe::math_forms_probe_kernel, dim3(blocks),
+                     dim3(psd::forms_probe::THREADS), 0, (hipStream_t) nullptr, form, set, n, d[0],
+                     d[1], d[2], d[3], d[4], d[5], d_rare);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  double *out[3] = {y0, y1, lz};
+  for (int k = 0; k < 3; k++)
+    if (out[k]) HIP_TRY(hipMemcpy(out[k], d[3 + k], bytes, hipMemcpyDeviceToHost));
+  if (rare) HIP_TRY(hipMemcpy(rare, d_rare, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (auto &q : d) (void)hipFree(q);
+  (void)hipFree(d_rare);
   return 0;
 }
 

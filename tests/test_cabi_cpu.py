@@ -102,6 +102,8 @@ def test_dp_without_gpu_fails_loudly(native, tmp_path):
     x = np.zeros(4)
     assert native.lib.peakseg_hip_math_probe(0, 4, x.ctypes.data, x.ctypes.data) == \
         native.ERROR_NO_HIP_DEVICE
+    assert native.lib.peakseg_hip_math_forms_probe(0, 0, 4, x.ctypes.data, None, None, x.ctypes.data,
+                                                   None, None, None) == native.ERROR_NO_HIP_DEVICE
 
 
 def test_product_never_touches_the_oracle():

@@ -36,6 +36,40 @@ def test_log_accuracy(oracle_det):
     assert _max_ulp(mp.log, xs, ys) < 1.0
 
 
+def test_exp_accuracy_at_the_edges(oracle_det):
+    """the arguments of tests/detmath_points.py: the rounding points of the table index, |x| = 708,
+    the thresholds of psd_exp_slow and subnormal results (whose unit is 2^-1074: math.ulp says so).
+    Measured: 0.58 ulp, at -709.77."""
+    import detmath_points as dp
+    mp.mp.prec = 200
+    xs = dp.exp_points()
+    ys = oracle_det.math("exp", xs)
+    inside = (xs >= dp.EXP_UNDERFLOW) & (xs <= dp.EXP_OVERFLOW)
+    assert inside.sum() > 16000 and np.sum(ys[inside] < dp.DBL_MIN) > 100
+    worst = _max_ulp(mp.exp, xs[inside], ys[inside])
+    print("exp at the edges: %.3f ulp" % worst)
+    assert worst < 1.0
+    assert np.all(ys[xs > dp.EXP_OVERFLOW] == np.inf) and np.all(ys[xs < dp.EXP_UNDERFLOW] == 0.0)
+    assert np.all(np.isnan(ys[np.isnan(xs)]))
+
+
+def test_log_accuracy_at_the_edges(oracle_det):
+    """the arguments of tests/detmath_points.py: both sides of every cell edge of the table and of
+    every table point in six binades, the neighbours of 1, 0.5, 2 and DBL_MIN, the ends of the range
+    and the subnormals.  Measured: 0.52 ulp."""
+    import detmath_points as dp
+    mp.mp.prec = 200
+    xs = np.concatenate([dp.log_cell_points(), dp.log_near_points()])
+    ys = oracle_det.math("log", xs)
+    worst = _max_ulp(mp.log, xs, ys)
+    print("log at the edges: %.3f ulp" % worst)
+    assert worst < 1.0
+    sp = dp.log_specials()
+    ys = oracle_det.math("log", sp)
+    assert np.all(ys[sp == 0.0] == -np.inf) and np.all(ys[sp == np.inf] == np.inf)
+    assert np.all(np.isnan(ys[(sp < 0.0) | np.isnan(sp)]))
+
+
 def test_special_values_match_libm(oracle_det, oracle_libm):
     sp = np.array([0.0, -0.0, 1.0, np.inf, -np.inf, np.nan, -1.0, 710.0, 709.78, -745.2,
                    -745.0, -800.0, 1e-320, 1e308, 2.0, 0.5])

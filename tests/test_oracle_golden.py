@@ -171,8 +171,12 @@ def test_division_repair_restores_the_ieee_quotient(oracle_det):
     """psd_div_repair (include/peakseg_detmath.h), what the device applies to the quotient of its
     own division sequence, run on the host: handed the IEEE quotient or either of its
     neighbours -- for random operands of both signs and many magnitudes, and for the operands
-    that come closest to midpoints -- it returns the IEEE quotient; zero, infinite and NaN
-    quotients pass through."""
+    that come closest to midpoints, all with NORMAL quotients -- it returns the IEEE quotient.
+    The quotients of x/0 and inf/x, zeros and NaNs pass through.  The infinite quotient of finite
+    operands (an overflow, in the four sign combinations) does not: its neighbour +-DBL_MAX has
+    the smaller residual and is returned, which the header documents as outside the contract of
+    psd_div and explains.  Subnormal quotients, whose residual is not exact, are
+    tests/test_detmath_forms_cpu.py's: there only a correct quotient is sure to stay."""
     import ctypes
     rng = np.random.default_rng(11)
     n = 400000
@@ -186,6 +190,7 @@ def test_division_repair_restores_the_ieee_quotient(oracle_det):
     a = np.concatenate([a, frac, [float.fromhex("0x1.6666666666663p-1")]])
     b = np.concatenate([b, near, [float.fromhex("0x1.ffffffffffffbp-1")]])
     want = a / b
+    assert np.all(np.abs(want) >= 2.0 ** -1022) and np.all(np.isfinite(want))
 
     def repair(q):
         x = np.ascontiguousarray(np.concatenate([q, a, b]))
@@ -202,4 +207,12 @@ def test_division_repair_restores_the_ieee_quotient(oracle_det):
         want = a / b
     got = repair(want)
     assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
-
+    # quotients that overflow: handed +-inf, the repair returns the documented +-DBL_MAX
+    import detmath_points
+    a, b = detmath_points.overflow_pairs()
+    with np.errstate(over="ignore"):
+        want = a / b
+    assert sorted(set(zip(np.sign(a), np.sign(b)))) == [(-1, -1), (-1, 1), (1, -1), (1, 1)]
+    assert np.all(np.isinf(want))
+    got = repair(want)
+    assert np.array_equal(got, np.copysign(detmath_points.DBL_MAX, want))
