@@ -593,6 +593,72 @@ int peakseg_hip_problem_set_packed_peak_clusters_download(
  * to its last, the download of the groups' cluster counts included */
 int peakseg_hip_peak_clusters_last_ms(float *ms);
 
+/* One common peak per window for all members of a group (PeakSegPipeline's PeakSegJoint step): the
+ * final peak calls of a project with several samples, which samples carry each peak, and the
+ * likelihood gains a differential analysis ranks by.  For a set made from dense counts or reads;
+ * group[] and the members as for pack_peak_clusters; member i has the extent
+ * [first_i, first_i + bases_i).
+ *   windows   n_windows[g] windows per group (host), window_start[g] / window_end[g] their int32
+ *             arrays (host, or with windows_on_device != 0 device addresses, read in place; one
+ *             call takes one kind).  With n_windows == NULL the call first runs pack_peak_clusters
+ *             on the resident tables (a SOLVED set) and window c of a group is its cluster c widened
+ *             by its own width on either side: [clusterStart - w, clusterEnd + w),
+ *             w = clusterEnd - clusterStart, in 64 bits.  A given window needs no solve.
+ *             A window is clipped to the intersection of the extents of all members of its group:
+ *             [ws, we), W = we - ws.  W < 3, or a group without members: no joint peak.
+ *   sums      C_i(x, y): the sum of member i's per-base counts over [x, y), exact int64;
+ *             T_i = C_i(ws, we)
+ *   gain      of a candidate (s, e), ws < s < e < we: L1 = s - ws, L2 = e - s, L3 = we - e and
+ *             S1, S2, S3 the member's sums over them.  The member is FEASIBLE iff S2 L1 > S1 L2 and
+ *             S2 L3 > S3 L2 (exact products).  t(S, L) = 0 for S = 0, else
+ *             double(S) * log(double(S) / double(L)) with the log of peakseg_detmath.h, a correctly
+ *             rounded division and conversions that round to nearest;
+ *             gain_i(s, e) = ((t(S1, L1) + t(S2, L2)) + t(S3, L3)) - t(T_i, W): the Poisson loss of
+ *             the flat model minus that of the three-segment model
+ *   G(s, e)   the sum over the feasible members, in member order, of max(0, gain_i(s, e) - penalty)
+ *   search    level 0: b the smallest power of two with n = ceil(W / b) <= 64; candidates
+ *             s = ws + i b, e = ws + j b, 1 <= i < j <= n - 1.  While b > 1: b' = b / 2, candidates
+ *             s = s* + p b', e = e* + q b' for p, q in -4 .. 4 with ws < s < e < we around the choice
+ *             (s*, e*) so far, then b = b'.  At every level the choice is the candidate with the
+ *             largest G, among equals the smallest s, then the smallest e (an exact comparison: the
+ *             schedule decides nothing).  A best G of 0 at level 0: no joint peak.  Otherwise the
+ *             peak is the last level's choice, objective its G, levels the levels run.
+ *   per window, group after group: windowStart, windowEnd (the clipped window; windowEnd =
+ *             windowStart where nothing is left), peakStart, peakEnd (-1: no joint peak; then
+ *             objective, samples_up, levels and the window's matrix entries are 0), samples_up,
+ *             levels (int32) and objective (double)
+ *   per (window, member), window-major as the cluster matrix: m_gain (double; 0 where the member is
+ *             infeasible at the peak), m_up (int32; 1 iff feasible and gain > penalty; samples_up is
+ *             their sum), m_sum (int64, S2), m_bases (int32, L2)
+ * windows_out[g], members_out[g] (n_groups entries, host, may be NULL) receive the windows and the
+ * members of group g.  All windows advance through the levels in lockstep: the number of launches
+ * depends on the widest window's log2 b only (peaksegdisk_amd/csrc/joint_peaks.h); a head of 16
+ * bytes is downloaded once after the first launch.
+ * Returns the total number of windows; -1 for a set that was not made from dense counts, or is not
+ * solved where n_windows == NULL; -ERROR_REGION_ARGUMENTS for a penalty that is negative or NaN, a
+ * bad group (as pack_peak_clusters), a negative n_windows[g], a NULL or misaligned array, or a given
+ * window with start >= end, with the group and the window named (host arrays are checked on the
+ * host, device arrays by the first launch); -ERROR_DEVICE_MEMORY when the call's tables do not fit
+ * (PEAKSEG_HIP_MAX_BYTES or the device), said before anything of them is allocated.  The device
+ * addresses stay valid until the set is solved again, this function is called again, or the set is
+ * destroyed; ..._download copies the columns (any may be NULL) and returns -1 when nothing is
+ * packed. */
+long long peakseg_hip_problem_set_pack_joint_peaks(
+    psd_problem_set *set, const int *first_chromStart, int n_groups, const int *group, double penalty,
+    const long long *n_windows, const int *const *window_start, const int *const *window_end,
+    int windows_on_device, long long *windows_out, long long *members_out,
+    const int **windowStart_dev, const int **windowEnd_dev, const int **peakStart_dev,
+    const int **peakEnd_dev, const double **objective_dev, const int **samples_up_dev,
+    const int **levels_dev, const double **m_gain_dev, const int **m_up_dev,
+    const long long **m_sum_dev, const int **m_bases_dev);
+int peakseg_hip_problem_set_packed_joint_peaks_download(
+    psd_problem_set *set, int *windowStart_out, int *windowEnd_out, int *peakStart_out,
+    int *peakEnd_out, double *objective_out, int *samples_up_out, int *levels_out, double *m_gain_out,
+    int *m_up_out, long long *m_sum_out, int *m_bases_out);
+/* milliseconds (HIP events) of the calling thread's last pack_joint_peaks: from its first launch to
+ * its last, the download of the head included (the cluster step of n_windows == NULL is not) */
+int peakseg_hip_joint_peaks_last_ms(float *ms);
+
 /* The fits of a penalty-learning regression (the model that penalty_model= takes): interval
  * regression with the squared hinge of margin 1, an L1 penalty on the weights and an unpenalised
  * intercept, for every regularization of a path and every fold of a cross-validation, in one launch

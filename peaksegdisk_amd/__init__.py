@@ -12,7 +12,7 @@ from .api import (PeakSegError, PeakSegFPOP_dir, PeakSegFPOP_df, PeakSegFPOP_fil
                   parallelSearch_dir_batch, writeBedGraph, targetInterval_dense,
                   targetInterval_reads, problem_features_dense, problem_features_reads,
                   predict_penalties, consensus_peaks_dense, consensus_peaks_reads,
-                  ConsensusPeaks)
+                  ConsensusPeaks, joint_peaks_dense, joint_peaks_reads, JointPeaks)
 from ._native import last_fanout  # noqa: F401
 from .grid import ProblemSet, read_labels_bed, features_from_stats  # noqa: F401
 from .fit import (PenaltyModelFit, fit_penalty_model, learn_penalty_model_dense,  # noqa: F401
@@ -28,4 +28,4 @@ __all__ = ["PeakSegFPOP_file", "PeakSegFPOP_dir", "PeakSegFPOP_df", "PeakSegFPOP
            "predict_penalties", "features_from_stats",
            "fit_penalty_model", "learn_penalty_model_dense", "learn_penalty_model_reads",
            "PenaltyModelFit", "consensus_peaks_dense", "consensus_peaks_reads", "ConsensusPeaks",
-           "PeakSegError"]
+           "joint_peaks_dense", "joint_peaks_reads", "JointPeaks", "PeakSegError"]

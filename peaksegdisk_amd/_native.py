@@ -269,6 +269,14 @@ def declare(lib):
         c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.peakseg_hip_peak_clusters_probe.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_pack_joint_peaks.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_int, c.c_void_p, c.c_void_p] + [c.POINTER(c.c_void_p)] * 11
+    lib.peakseg_hip_problem_set_pack_joint_peaks.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_joint_peaks_download.argtypes = [c.c_void_p] * 12
+    lib.peakseg_hip_problem_set_packed_joint_peaks_download.restype = c.c_int
+    lib.peakseg_hip_joint_peaks_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_joint_peaks_last_ms.restype = c.c_int
     lib.peakseg_hip_search_place_penalties.argtypes = [
         c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
     lib.peakseg_hip_search_place_penalties.restype = c.c_int
@@ -320,6 +328,8 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_pack_peak_clusters",
     "peakseg_hip_problem_set_packed_peak_clusters_download",
     "peakseg_hip_peak_clusters_last_ms", "peakseg_hip_peak_clusters_probe",
+    "peakseg_hip_problem_set_pack_joint_peaks",
+    "peakseg_hip_problem_set_packed_joint_peaks_download", "peakseg_hip_joint_peaks_last_ms",
 ]
 
 if not os.path.exists(LIB_PATH):

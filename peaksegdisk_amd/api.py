@@ -398,14 +398,15 @@ LABEL_TOTALS = ["errors", "fp", "fn", "possible.fp", "possible.fn"]
 
 
 def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, penalty_model=None,
-                     cluster_groups=None):
+                     cluster_groups=None, joint_penalty=None):
     """What PeakSegFPOP_dense and PeakSegFPOP_reads share: the problems of `pens` (one list per
     contig), the set -- make_set(problems) -> (ProblemSet, chromStart of each contig's first
     base) --, its solution, and the reference's data frames, nested as `pens` is.
     penalty_model: `pens` holds one placeholder (Inf) per contig; every problem gets the penalty
     the model predicts from the set's coverage features before the one solve.
     cluster_groups: one group per problem; the solved set's ProblemSet.peak_clusters() is returned
-    with the data frames, as (frames, clusters)."""
+    with the data frames, as (frames, clusters); with joint_penalty its ProblemSet.joint_peaks() on
+    the clusters' windows too, as (frames, clusters, joint)."""
     if labels is not None:
         labels = _label_lists(labels, len(pens), single, "contig")
     problems, pen_strs = [], []
@@ -447,6 +448,9 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, p
         if cluster_groups is not None:
             try:
                 clusters = pset.peak_clusters(cluster_groups, first_chromStart=chrom_starts)
+                if joint_penalty is not None:
+                    clusters = (clusters, pset.joint_peaks(cluster_groups, penalty=joint_penalty,
+                                                           first_chromStart=chrom_starts))
             except RuntimeError as e:
                 raise PeakSegError(getattr(e, "status", _native.ERROR_DEVICE_SOLVER), str(e))
         rows = [(pset.loss(p), pset.result(p)) for p in range(len(problems))]
@@ -488,7 +492,9 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, p
         out.append(flat[o:o + len(q)])
         o += len(q)
     out = out[0] if single else out
-    return out if cluster_groups is None else (out, clusters)
+    if cluster_groups is None:
+        return out
+    return (out,) + clusters if joint_penalty is not None else (out, clusters)
 
 
 def _penalty_source(penalties, penalty_model, n_contigs, noun):
@@ -718,6 +724,88 @@ def consensus_peaks_reads(reads, penalties=None, penalty_model=None, groups=None
     solved = _solve_dense_set(make_set, pens, "chrUnknown", False, False, "<aligned reads>", None,
                               penalty_model, cluster_groups=groups)
     return _consensus_result(solved, groups, chrom)
+
+
+# ---- joint peaks of several samples (additive) -------------------------
+
+class JointPeaks(ConsensusPeaks):
+    """What joint_peaks_dense / joint_peaks_reads return: a ConsensusPeaks whose groups also hold
+    "joint": a data frame chrom, windowStart, windowEnd, peakStart, peakEnd, objective, samples_up,
+    levels with one row per consensus peak (its window is the cluster widened by its own width on
+    either side; peakStart = peakEnd = -1: no joint peak), and "gain", "up", "joint_sum",
+    "joint_bases": (clusters, samples of the group) arrays -- each sample's likelihood gain at the
+    joint peak, whether it carries it, and its coverage and bases under it.
+    joint, gain, up: those of the only group (ValueError when there are several)."""
+
+    joint = property(lambda self: self._only("joint"))
+    gain = property(lambda self: self._only("gain"))
+    up = property(lambda self: self._only("up"))
+
+
+def _joint_result(solved, groups, chrom):
+    fits, clusters, joint = solved
+    out = _consensus_result((fits, clusters), groups, chrom)
+    for g, entry in enumerate(joint):
+        frame = entry["joint"].copy()
+        frame.insert(0, "chrom", chrom[g])
+        out.groups[g].update({"joint": frame, "gain": entry["gain"], "up": entry["up"],
+                              "joint_sum": entry["sum"], "joint_bases": entry["bases"]})
+    return JointPeaks(out.groups, out.fits)
+
+
+def _joint_penalty(joint_penalty):
+    value = float(joint_penalty)
+    if not value >= 0.0:
+        raise ValueError("joint_penalty %r is negative or not a number" % (joint_penalty,))
+    return value
+
+
+def joint_peaks_dense(count_vecs, penalties=None, penalty_model=None, groups=None, joint_penalty=0.0,
+                      chrom="chrUnknown", chrom_starts=None, device=0):
+    """consensus_peaks_dense with the next step behind it, still in one process and with nothing
+    downloaded in between: for every consensus peak one common peak is fitted at base resolution to
+    all samples of its group at once (ProblemSet.joint_peaks; PeakSegPipeline's PeakSegJoint step),
+    and every sample is called up or flat there.  joint_penalty >= 0: the price of one more sample
+    with a peak.  The other arguments as consensus_peaks_dense.  Returns a JointPeaks."""
+    from .grid import ProblemSet
+    if isinstance(count_vecs, np.ndarray) and count_vecs.ndim == 1 or hasattr(count_vecs, "data_ptr"):
+        raise ValueError("count.vecs: a list of vectors, one per sample")
+    vecs = list(count_vecs)
+    joint_penalty = _joint_penalty(joint_penalty)
+    pens, groups, chrom = _consensus_arguments(len(vecs), penalties, penalty_model, groups, chrom)
+    contigs = [_int32_vector(v) for v in vecs]
+    if chrom_starts is None:
+        chrom_starts = [0] * len(vecs)
+    if len(chrom_starts) != len(vecs):
+        raise ValueError("chrom.starts: one per sample")
+    solved = _solve_dense_set(
+        lambda problems: (ProblemSet.from_dense(contigs, problems, device=device), chrom_starts),
+        pens, "chrUnknown", False, False, "<dense counts>", None, penalty_model, cluster_groups=groups,
+        joint_penalty=joint_penalty)
+    return _joint_result(solved, groups, chrom)
+
+
+def joint_peaks_reads(reads, penalties=None, penalty_model=None, groups=None, joint_penalty=0.0,
+                      chrom="chrUnknown", extents=None, bases_counted="each", device=0):
+    """joint_peaks_dense with the pile-up in front of it: reads, extents and bases_counted as
+    consensus_peaks_reads takes them."""
+    from .grid import ProblemSet
+    if len(reads) and not isinstance(reads[0], (tuple, list)):
+        raise ValueError("reads: a list of samples, each (chromStart, chromEnd[, count])")
+    samples = list(reads)
+    joint_penalty = _joint_penalty(joint_penalty)
+    pens, groups, chrom = _consensus_arguments(len(samples), penalties, penalty_model, groups, chrom)
+    names = ("chromStart", "chromEnd", "count")
+    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
+               for entry in samples]
+
+    def make_set(problems):
+        pset = ProblemSet.from_reads(contigs, problems, extents=extents,
+                                     bases_counted=bases_counted, device=device)
+        return pset, pset.contig_starts
+    solved = _solve_dense_set(make_set, pens, "chrUnknown", False, False, "<aligned reads>", None,
+                              penalty_model, cluster_groups=groups, joint_penalty=joint_penalty)
+    return _joint_result(solved, groups, chrom)
 
 
 # ---- coverage features and learned penalties (additive; DESIGN.md section 13) ----------------

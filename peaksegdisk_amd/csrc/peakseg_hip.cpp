@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, joint, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -92,6 +92,8 @@
 #include "region_stats.h"
 /* the clusters of overlapping peaks over the members of a group, and the cluster-by-member matrix */
 #include "peak_clusters.h"
+/* one common peak per window for all members of a group: the level-by-level search */
+#include "joint_peaks.h"
 /* tests only: every form of the deterministic exp / log, element by element */
 #include "math_forms_probe.h"
 
@@ -134,6 +136,7 @@
 #include "peakseg_fit.h"
 #include "peakseg_regions.h"
 #include "peakseg_clusters.h"
+#include "peakseg_joint.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -185,7 +188,7 @@ extern "C" void peakseg_hip_problem_set_destroy(psd_problem_set *s) {
     if (e) (void)hipEventDestroy(e);
   for (auto &e : s->features.ev)
     if (e) (void)hipEventDestroy(e);
-  for (auto *ev : {s->regions.ev, s->clusters.ev, s->clusters.matrix.ev})
+  for (auto *ev : {s->regions.ev, s->clusters.ev, s->clusters.matrix.ev, s->joint.ev, s->joint.fold.ev})
     for (int k = 0; k < 2; k++)
       if (ev[k]) (void)hipEventDestroy(ev[k]);
   if (s->stream) (void)hipStreamDestroy(s->stream);

@@ -123,6 +123,33 @@ struct ClusterTable {
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
+/* What peakseg_hip_problem_set_pack_joint_peaks keeps (peakseg_joint.h): the groups and members of a
+ * call, the windows with their peaks, the regions of a level and their fold, and the matrix.  Every
+ * array grows to what the largest call so far needed. */
+struct JointTable {
+  int *member0 = nullptr;                                        /* groups + 1 */
+  long long *win_off = nullptr, *entry_off = nullptr, *lo = nullptr, *hi = nullptr; /* groups + 1 */
+  const int **g_start = nullptr, **g_end = nullptr;              /* groups + 1 */
+  long long group_capacity = 0;
+  int *member_contig = nullptr;                                  /* per member */
+  long long member_capacity = 0;
+  int *d_windows = nullptr;                                      /* 2 x windows: as given (host arrays) */
+  int *w_group = nullptr, *ws = nullptr, *we = nullptr, *b = nullptr, *s = nullptr, *e = nullptr,
+      *levels = nullptr, *samples_up = nullptr;                  /* per window */
+  double *objective = nullptr;
+  long long window_capacity = 0;
+  psd::joint::Head *head = nullptr;
+  long long *total = nullptr;                                    /* per entry */
+  double *m_gain = nullptr;
+  int *m_up = nullptr, *m_bases = nullptr;
+  long long *m_sum = nullptr;
+  int *region_start = nullptr, *region_end = nullptr, *region_contig = nullptr; /* 64 per entry */
+  long long entry_capacity = 0;
+  RegionTable fold;     /* the fold of a level's regions */
+  long long windows = -1, entries = -1; /* of the last call (-1: nothing packed) */
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
 struct psd_problem_set {
   /* geometry: the contigs, the problems and where their tables start */
   int device = 0;
@@ -189,6 +216,7 @@ struct psd_problem_set {
   FeatureTable features; /* (sets made from dense counts) */
   RegionTable regions; /* (sets made from dense counts) */
   ClusterTable clusters; /* (sets made from dense counts) */
+  JointTable joint; /* (sets made from dense counts) */
 
   /* Sets made from dense counts (peakseg_hip_problem_set_create_dense): run_end[] next to count[]
    * and weight[], the sum of each contig's counts, and which contigs are constant.  Their trivial

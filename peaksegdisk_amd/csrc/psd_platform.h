@@ -234,6 +234,23 @@ PSD_D T *uniform_p(T *p) {
 #endif
 }
 
+/* the exact product of two 64-bit words: its low word, and the high one in `hi` (two 64-bit
+ * multiplies, v_mul_hi among them; the emulator has the 128-bit type) */
+#ifdef PSD_EMU
+PSD_D unsigned long long mul_wide_u64(unsigned long long a, unsigned long long b,
+                                      unsigned long long &hi) {
+  const unsigned __int128 p = (unsigned __int128)a * b;
+  hi = (unsigned long long)(p >> 64);
+  return (unsigned long long)p;
+}
+#else
+PSD_D unsigned long long mul_wide_u64(unsigned long long a, unsigned long long b,
+                                      unsigned long long &hi) {
+  hi = __umul64hi(a, b);
+  return a * b;
+}
+#endif
+
 PSD_D int popc64(unsigned long long m) { return __builtin_popcountll(m); }
 /* index of the lowest set bit; m != 0 */
 PSD_D int ctz64(unsigned long long m) { return __builtin_ctzll(m); }

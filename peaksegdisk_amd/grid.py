@@ -621,6 +621,115 @@ class ProblemSet:
             result.append(entry)
         return result
 
+    def joint_peaks(self, groups, penalty=0.0, windows=None, first_chromStart=None,
+                    torch_device=None):
+        """One common peak per window for all members of a group, and which members carry it
+        (peakseg_hip_problem_set_pack_joint_peaks; include/peaksegdisk_hip.h has the definitions:
+        PeakSegPipeline's PeakSegJoint step), on the device from the resident runs of a set made by
+        from_dense or from_reads.  groups as for peak_clusters().  penalty >= 0: the price of one
+        more member with a peak.  windows: None -- the windows are the clusters of peak_clusters()
+        (a solved set), each widened by its own width on either side -- or a list over GROUPS of
+        (start, end), 1-d contiguous int32 numpy arrays or torch tensors (an empty entry or None: no
+        windows); tensors on the set's cuda device are read in place; one call takes one kind of
+        memory; no solve is needed.  Every window is clipped to the extent all members of its group
+        share.  first_chromStart as in segment_columns().  Without torch_device: a list over groups
+        of {"members": the problems' indices, "joint": a data frame with the columns windowStart,
+        windowEnd, peakStart, peakEnd, objective, samples_up, levels (peakStart = peakEnd = -1: no
+        joint peak), and "gain" (float64), "up" (int32), "sum" (int64), "bases" (int32): (windows,
+        members) arrays}.  With torch_device: (windows int64 numpy[n_groups + 1], entries int64
+        numpy[n_groups + 1], windowStart, windowEnd, peakStart, peakEnd, objective, samples_up,
+        levels, m_gain, m_up, m_sum, m_bases) where the eleven are tensors that alias the library's
+        buffers (group g's windows are windows[g]:windows[g + 1], its matrix entries
+        entries[g]:entries[g + 1], window-major); they are valid until the next solve(), the next
+        joint_peaks() or close().  A window with start >= end, and a penalty that is negative or
+        NaN, raise RuntimeError with .status 22."""
+        group = np.ascontiguousarray(groups, dtype=np.int32) if len(groups) else np.zeros(0, np.int32)
+        if group.shape != (len(self.problems),):
+            raise ValueError("joint_peaks: one group per problem (%d values, %d problems)"
+                             % (group.size, len(self.problems)))
+        if not np.array_equal(group, np.asarray(groups)):
+            raise ValueError("joint_peaks: groups must be integers")
+        n_groups = int(group.max()) + 1 if group.size and group.max() >= 0 else 0
+        first = self._first_chromStart(first_chromStart)
+        keep, sides, lengths = [], [], None
+        ptrs = ([], [])
+        if windows is not None:
+            if len(windows) != n_groups:
+                raise ValueError("joint_peaks: one entry of windows per group (%d entries, %d groups)"
+                                 % (len(windows), n_groups))
+            lengths = []
+            for g, entry in enumerate(windows):
+                if entry is None or len(entry) == 0:
+                    lengths.append(0)
+                    for q in ptrs:
+                        q.append(0)
+                    continue
+                if len(entry) != 2:
+                    raise ValueError("joint_peaks: the windows of group %d are not (start, end)" % g)
+                n = None
+                for j in range(2):
+                    ptr, m, side, ref = _dense_pointer(
+                        g, entry[j], self.device, "joint_peaks: group %d window " + ("start", "end")[j])
+                    if n is not None and m != n:
+                        raise ValueError("joint_peaks: group %d has %d window starts and %d ends"
+                                         % (g, n, m))
+                    n = m
+                    keep.append(ref)
+                    sides.append((side, g))
+                    ptrs[j].append(ptr if m else 0)
+                lengths.append(n)
+            for side, g in sides:
+                if side != sides[0][0]:
+                    raise ValueError("joint_peaks: group %d is in %s memory but group %d is in %s "
+                                     "memory; one call takes one kind" % (g, side, sides[0][1], sides[0][0]))
+        room = max(n_groups, 1)
+        k = np.zeros(room, dtype=np.int64)
+        m = np.zeros(room, dtype=np.int64)
+        out = [ctypes.c_void_p() for _ in range(11)]
+        given = []
+        if lengths is not None:
+            given = [(ctypes.c_longlong * room)(*lengths)] + [(ctypes.c_void_p * room)(*q) for q in ptrs]
+        total = self._lib.peakseg_hip_problem_set_pack_joint_peaks(
+            self._h, first.ctypes.data if first is not None else None, n_groups, group.ctypes.data,
+            float(penalty), *([ctypes.addressof(a) for a in given] if given else [None, None, None]),
+            1 if sides and sides[0][0] == "device" else 0, k.ctypes.data, m.ctypes.data,
+            *[ctypes.byref(q) for q in out])
+        del keep  # (the library holds no reference to the caller's buffers after the call)
+        if total < 0:
+            self._raise_status("pack_joint_peaks", total)
+        total = int(total)
+        k, m = k[:n_groups], m[:n_groups]
+        w_off = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
+        e_off = np.concatenate([[0], np.cumsum(k * m)]).astype(np.int64)
+        entries = int(e_off[-1])
+        dtypes = (np.int32,) * 4 + (np.float64, np.int32, np.int32, np.float64, np.int32, np.int64,
+                                    np.int32)
+        sizes = (total,) * 7 + (entries,) * 4
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            return (w_off, e_off) + tuple(device_array(q.value or 0, n, dt, dev)
+                                          for q, n, dt in zip(out, sizes, dtypes))
+        cols = [np.empty(n, dtype=dt) for n, dt in zip(sizes, dtypes)]
+        if self._lib.peakseg_hip_problem_set_packed_joint_peaks_download(
+                self._h, *[a.ctypes.data for a in cols]) != 0:
+            raise RuntimeError("packed_joint_peaks_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        import pandas as pd
+        result = []
+        for g in range(n_groups):
+            rows = slice(int(w_off[g]), int(w_off[g + 1]))
+            cells = slice(int(e_off[g]), int(e_off[g + 1]))
+            entry = {"members": np.flatnonzero(group == g),
+                     "joint": pd.DataFrame({name: cols[j][rows] for j, name in enumerate(
+                         ("windowStart", "windowEnd", "peakStart", "peakEnd", "objective",
+                          "samples_up", "levels"))})}
+            for j, name in enumerate(("gain", "up", "sum", "bases")):
+                entry[name] = cols[7 + j][cells].reshape(int(k[g]), int(m[g]))
+            result.append(entry)
+        return result
+
     def _coverage_stats(self, ranks, torch_device=None):
         """one peakseg_hip_problem_set_pack_coverage_stats: ranks int64 [n_contigs, k], k at most
         max_ranks -> (value int32 [n_contigs, k], moments uint64 [n_contigs, 6]); with torch_device
