@@ -659,6 +659,80 @@ int peakseg_hip_problem_set_packed_joint_peaks_download(
  * its last, the download of the head included (the cluster step of n_windows == NULL is not) */
 int peakseg_hip_joint_peaks_last_ms(float *ms);
 
+/* pack_joint_peaks at n_penalties penalties in one call: model (p, w) is exactly what
+ * pack_joint_peaks returns for window w at penalties[p], bit for bit, in every column; all the
+ * definitions above hold unchanged per penalty (feasibility, t, gain, G added in member order, the
+ * three-key choice, the levels).  What does not depend on the penalty -- the bins of level 0 and
+ * their fold, the prefix sums, t(T, W), the feasibility test and the gain of every (candidate,
+ * member) -- is computed once per window; from level 1 on every penalty refines its own choice, and
+ * a penalty without a peak idles.
+ *   penalties 1 <= n_penalties <= peakseg_hip_joint_path_max_penalties() (16) doubles >= 0 (host), in
+ *             any order; repeats, 0 and +Inf (no joint peak anywhere) are allowed
+ *   layout    penalty-major: the per-window columns at p * windows + w (windows: the value
+ *             returned), the per-(window, member) columns at p * entries + entry (entries: the sum
+ *             over the groups of windows_out[g] * members_out[g])
+ * The other arguments, and the refusals, are pack_joint_peaks's; -ERROR_REGION_ARGUMENTS also for
+ * n_penalties out of range and for a penalty that is negative or NaN, with its index named;
+ * -ERROR_DEVICE_MEMORY, before anything is allocated, when the tables -- n_penalties times those of
+ * pack_joint_peaks, 18 n_penalties (at least 64) regions per entry, and for groups of more than 64
+ * members 2048 doubles per (window, penalty) -- do not fit.  The number of launches is that of one
+ * pack_joint_peaks: it depends on the widest window's levels only, not on n_penalties
+ * (peaksegdisk_amd/csrc/joint_path.h).
+ * The call keeps buffers of its own: a later pack_joint_peaks does not touch what it packed, nor
+ * does it touch what pack_joint_peaks packed.  The device addresses stay valid until the set is
+ * solved again, this function is called again, or the set is destroyed; ..._download copies the
+ * columns (any may be NULL; n_penalties times as many entries each) and returns -1 when nothing is
+ * packed. */
+int peakseg_hip_joint_path_max_penalties(void);
+long long peakseg_hip_problem_set_pack_joint_path(
+    psd_problem_set *set, const int *first_chromStart, int n_groups, const int *group,
+    int n_penalties, const double *penalties, const long long *n_windows,
+    const int *const *window_start, const int *const *window_end, int windows_on_device,
+    long long *windows_out, long long *members_out, const int **windowStart_dev,
+    const int **windowEnd_dev, const int **peakStart_dev, const int **peakEnd_dev,
+    const double **objective_dev, const int **samples_up_dev, const int **levels_dev,
+    const double **m_gain_dev, const int **m_up_dev, const long long **m_sum_dev,
+    const int **m_bases_dev);
+int peakseg_hip_problem_set_packed_joint_path_download(
+    psd_problem_set *set, int *windowStart_out, int *windowEnd_out, int *peakStart_out,
+    int *peakEnd_out, double *objective_out, int *samples_up_out, int *levels_out, double *m_gain_out,
+    int *m_up_out, long long *m_sum_out, int *m_bases_out);
+/* milliseconds (HIP events) of the calling thread's last pack_joint_path: from its first launch to
+ * its last, the download of the head included (the cluster step of n_windows == NULL is not) */
+int peakseg_hip_joint_path_last_ms(float *ms);
+
+/* The label errors of every model of the set's packed joint path (-1 without one), counted on the
+ * device from its columns, in integers only: the same result whatever the schedule.
+ *   labels    n_labels[q] labels per PROBLEM (host) and label_start[q] / label_end[q] /
+ *             label_annotation[q], int32 arrays (host, or with labels_on_device != 0 device
+ *             addresses, read in place; one call takes one kind), in genomic coordinates, the ones
+ *             the joint peaks are in; annotation codes 0 noPeaks, 1 peakStart, 2 peakEnd, 3 peaks
+ *   peaks     of problem q in model p: the joint peaks [peakStart, peakEnd) of the windows w of q's
+ *             group with peakStart >= 0 and m_up[p, w, member of q] == 1.  Every window's peak
+ *             counts, also where the peaks of two given windows overlap or coincide.  A problem in
+ *             no group has no peaks in any model.
+ *   counted   count, fp and fn of a label by the relations and rules of pack_label_errors
+ *   per (penalty, label), penalty-major, within a penalty problem after problem in the order given:
+ *             count, fp, fn (int32)
+ *   per (penalty, problem): errors, fp, fn, possible_fp, possible_fn (int32, 5 per entry)
+ *   per penalty: the same five as int64
+ * Returns the number of labels of one penalty; -ERROR_LABEL_ARGUMENTS as pack_label_errors, with
+ * the problem and the label named (host arrays are checked on the host, device arrays by the first
+ * launch).  Two launches, however many penalties, problems, labels and windows
+ * (peaksegdisk_amd/csrc/joint_labels.h).  The device addresses stay valid until the next
+ * pack_joint_path, this function is called again, or the set is destroyed; ..._download copies the
+ * columns (any may be NULL) and returns -1 when nothing is packed. */
+long long peakseg_hip_problem_set_pack_joint_label_errors(
+    psd_problem_set *set, const long long *n_labels, const int *const *label_start,
+    const int *const *label_end, const int *const *label_annotation, int labels_on_device,
+    const int **count_dev, const int **fp_dev, const int **fn_dev, const int **problem_totals_dev,
+    const long long **model_totals_dev);
+int peakseg_hip_problem_set_packed_joint_label_errors_download(
+    psd_problem_set *set, int *count_out, int *fp_out, int *fn_out, int *problem_totals_out,
+    long long *model_totals_out);
+/* milliseconds (HIP events) of the calling thread's last pack_joint_label_errors */
+int peakseg_hip_joint_label_errors_last_ms(float *ms);
+
 /* The fits of a penalty-learning regression (the model that penalty_model= takes): interval
  * regression with the squared hinge of margin 1, an L1 penalty on the weights and an unpenalised
  * intercept, for every regularization of a path and every fold of a cross-validation, in one launch

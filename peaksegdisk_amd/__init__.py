@@ -12,9 +12,12 @@ from .api import (PeakSegError, PeakSegFPOP_dir, PeakSegFPOP_df, PeakSegFPOP_fil
                   parallelSearch_dir_batch, writeBedGraph, targetInterval_dense,
                   targetInterval_reads, problem_features_dense, problem_features_reads,
                   predict_penalties, consensus_peaks_dense, consensus_peaks_reads,
-                  ConsensusPeaks, joint_peaks_dense, joint_peaks_reads, JointPeaks)
+                  ConsensusPeaks, joint_peaks_dense, joint_peaks_reads, JointPeaks,
+                  joint_target_interval_dense, joint_target_interval_reads,
+                  learn_joint_penalty_dense, learn_joint_penalty_reads)
 from ._native import last_fanout  # noqa: F401
 from .grid import ProblemSet, read_labels_bed, features_from_stats  # noqa: F401
+from .joint_target import JointSearch, JointTargetInterval, joint_target_interval  # noqa: F401
 from .fit import (PenaltyModelFit, fit_penalty_model, learn_penalty_model_dense,  # noqa: F401
                   learn_penalty_model_reads)
 
@@ -28,4 +31,6 @@ __all__ = ["PeakSegFPOP_file", "PeakSegFPOP_dir", "PeakSegFPOP_df", "PeakSegFPOP
            "predict_penalties", "features_from_stats",
            "fit_penalty_model", "learn_penalty_model_dense", "learn_penalty_model_reads",
            "PenaltyModelFit", "consensus_peaks_dense", "consensus_peaks_reads", "ConsensusPeaks",
-           "joint_peaks_dense", "joint_peaks_reads", "JointPeaks", "PeakSegError"]
+           "joint_peaks_dense", "joint_peaks_reads", "JointPeaks", "joint_target_interval_dense",
+           "joint_target_interval_reads", "learn_joint_penalty_dense", "learn_joint_penalty_reads",
+           "JointSearch", "JointTargetInterval", "joint_target_interval", "PeakSegError"]

@@ -277,6 +277,24 @@ def declare(lib):
     lib.peakseg_hip_problem_set_packed_joint_peaks_download.restype = c.c_int
     lib.peakseg_hip_joint_peaks_last_ms.argtypes = [c.POINTER(c.c_float)]
     lib.peakseg_hip_joint_peaks_last_ms.restype = c.c_int
+    lib.peakseg_hip_joint_path_max_penalties.argtypes = []
+    lib.peakseg_hip_joint_path_max_penalties.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_joint_path.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_int, c.c_void_p, c.c_void_p] + [c.POINTER(c.c_void_p)] * 11
+    lib.peakseg_hip_problem_set_pack_joint_path.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_joint_path_download.argtypes = [c.c_void_p] * 12
+    lib.peakseg_hip_problem_set_packed_joint_path_download.restype = c.c_int
+    lib.peakseg_hip_joint_path_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_joint_path_last_ms.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_joint_label_errors.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int] + \
+        [c.POINTER(c.c_void_p)] * 5
+    lib.peakseg_hip_problem_set_pack_joint_label_errors.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_joint_label_errors_download.argtypes = [c.c_void_p] * 6
+    lib.peakseg_hip_problem_set_packed_joint_label_errors_download.restype = c.c_int
+    lib.peakseg_hip_joint_label_errors_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_joint_label_errors_last_ms.restype = c.c_int
     lib.peakseg_hip_search_place_penalties.argtypes = [
         c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
     lib.peakseg_hip_search_place_penalties.restype = c.c_int
@@ -330,6 +348,11 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_peak_clusters_last_ms", "peakseg_hip_peak_clusters_probe",
     "peakseg_hip_problem_set_pack_joint_peaks",
     "peakseg_hip_problem_set_packed_joint_peaks_download", "peakseg_hip_joint_peaks_last_ms",
+    "peakseg_hip_joint_path_max_penalties", "peakseg_hip_problem_set_pack_joint_path",
+    "peakseg_hip_problem_set_packed_joint_path_download", "peakseg_hip_joint_path_last_ms",
+    "peakseg_hip_problem_set_pack_joint_label_errors",
+    "peakseg_hip_problem_set_packed_joint_label_errors_download",
+    "peakseg_hip_joint_label_errors_last_ms",
 ]
 
 if not os.path.exists(LIB_PATH):

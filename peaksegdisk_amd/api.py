@@ -398,7 +398,7 @@ LABEL_TOTALS = ["errors", "fp", "fn", "possible.fp", "possible.fn"]
 
 
 def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, penalty_model=None,
-                     cluster_groups=None, joint_penalty=None):
+                     cluster_groups=None, joint_penalty=None, joint_search=None):
     """What PeakSegFPOP_dense and PeakSegFPOP_reads share: the problems of `pens` (one list per
     contig), the set -- make_set(problems) -> (ProblemSet, chromStart of each contig's first
     base) --, its solution, and the reference's data frames, nested as `pens` is.
@@ -406,7 +406,9 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, p
     the model predicts from the set's coverage features before the one solve.
     cluster_groups: one group per problem; the solved set's ProblemSet.peak_clusters() is returned
     with the data frames, as (frames, clusters); with joint_penalty its ProblemSet.joint_peaks() on
-    the clusters' windows too, as (frames, clusters, joint)."""
+    the clusters' windows too, as (frames, clusters, joint); with joint_search -- the keyword
+    arguments of joint_target.joint_target_interval, `labels` among them -- that search on the
+    clusters' windows instead, as (frames, clusters, JointTargetInterval)."""
     if labels is not None:
         labels = _label_lists(labels, len(pens), single, "contig")
     problems, pen_strs = [], []
@@ -451,6 +453,10 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, p
                 if joint_penalty is not None:
                     clusters = (clusters, pset.joint_peaks(cluster_groups, penalty=joint_penalty,
                                                            first_chromStart=chrom_starts))
+                elif joint_search is not None:
+                    from .joint_target import joint_target_interval
+                    clusters = (clusters, joint_target_interval(
+                        pset, cluster_groups, first_chromStart=chrom_starts, **joint_search))
             except RuntimeError as e:
                 raise PeakSegError(getattr(e, "status", _native.ERROR_DEVICE_SOLVER), str(e))
         rows = [(pset.loss(p), pset.result(p)) for p in range(len(problems))]
@@ -494,7 +500,9 @@ def _solve_dense_set(make_set, pens, chrom, stats, single, label, labels=None, p
     out = out[0] if single else out
     if cluster_groups is None:
         return out
-    return (out,) + clusters if joint_penalty is not None else (out, clusters)
+    if joint_penalty is not None or joint_search is not None:
+        return (out,) + clusters
+    return (out, clusters)
 
 
 def _penalty_source(penalties, penalty_model, n_contigs, noun):
@@ -806,6 +814,86 @@ def joint_peaks_reads(reads, penalties=None, penalty_model=None, groups=None, jo
     solved = _solve_dense_set(make_set, pens, "chrUnknown", False, False, "<aligned reads>", None,
                               penalty_model, cluster_groups=groups, joint_penalty=joint_penalty)
     return _joint_result(solved, groups, chrom)
+
+
+# ---- the joint penalty learned from labels (additive) -------------------
+
+def _joint_search(labels, n_samples, width, max_rounds, tol):
+    from .joint_target import DEFAULT_TOL, DEFAULT_WIDTH
+    tol = DEFAULT_TOL if tol is None else float(tol)
+    if not tol > 0:
+        raise ValueError("tol %r: a positive number" % (tol,))
+    if int(max_rounds) < 2:
+        raise ValueError("max_rounds %r: at least 2 (penalty 0, then the ladder)" % (max_rounds,))
+    return {"labels": _label_lists(labels, n_samples, False, "sample"),
+            "width": DEFAULT_WIDTH if width is None else int(width), "max_rounds": int(max_rounds),
+            "tol": tol}
+
+
+def joint_target_interval_dense(count_vecs, labels, penalties=None, penalty_model=None, groups=None,
+                                chrom="chrUnknown", chrom_starts=None, device=0, width=None,
+                                max_rounds=20, tol=None):
+    """The interval of log(joint penalty) whose joint models have the fewest label errors: the
+    single-sample solve and the clusters' windows exactly as joint_peaks_dense has them, then the
+    search of joint_target.py on the resident set -- one ProblemSet.joint_path and one
+    ProblemSet.joint_label_errors per round, nothing else downloaded.  labels: one entry per SAMPLE,
+    (chromStart, chromEnd, annotation) in genomic coordinates, None for a sample without labels;
+    annotation as ProblemSet.label_errors takes it.  width: the penalties of a round (default 8, at
+    most 16); tol: a flank is closed when its two penalties are within a factor 1 + tol (default
+    0.05).  The other arguments as joint_peaks_dense.  Returns (JointTargetInterval,
+    ConsensusPeaks): the interval, and the single-sample fits with the clusters searched."""
+    from .grid import ProblemSet
+    if isinstance(count_vecs, np.ndarray) and count_vecs.ndim == 1 or hasattr(count_vecs, "data_ptr"):
+        raise ValueError("count.vecs: a list of vectors, one per sample")
+    vecs = list(count_vecs)
+    search = _joint_search(labels, len(vecs), width, max_rounds, tol)
+    pens, groups, chrom = _consensus_arguments(len(vecs), penalties, penalty_model, groups, chrom)
+    contigs = [_int32_vector(v) for v in vecs]
+    if chrom_starts is None:
+        chrom_starts = [0] * len(vecs)
+    if len(chrom_starts) != len(vecs):
+        raise ValueError("chrom.starts: one per sample")
+    fits, clusters, interval = _solve_dense_set(
+        lambda problems: (ProblemSet.from_dense(contigs, problems, device=device), chrom_starts),
+        pens, "chrUnknown", False, False, "<dense counts>", None, penalty_model, cluster_groups=groups,
+        joint_search=search)
+    return interval, _consensus_result((fits, clusters), groups, chrom)
+
+
+def joint_target_interval_reads(reads, labels, penalties=None, penalty_model=None, groups=None,
+                                chrom="chrUnknown", extents=None, bases_counted="each", device=0,
+                                width=None, max_rounds=20, tol=None):
+    """joint_target_interval_dense with the pile-up in front of it: reads, extents and
+    bases_counted as consensus_peaks_reads takes them."""
+    from .grid import ProblemSet
+    if len(reads) and not isinstance(reads[0], (tuple, list)):
+        raise ValueError("reads: a list of samples, each (chromStart, chromEnd[, count])")
+    samples = list(reads)
+    search = _joint_search(labels, len(samples), width, max_rounds, tol)
+    pens, groups, chrom = _consensus_arguments(len(samples), penalties, penalty_model, groups, chrom)
+    names = ("chromStart", "chromEnd", "count")
+    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
+               for entry in samples]
+
+    def make_set(problems):
+        pset = ProblemSet.from_reads(contigs, problems, extents=extents,
+                                     bases_counted=bases_counted, device=device)
+        return pset, pset.contig_starts
+    fits, clusters, interval = _solve_dense_set(
+        make_set, pens, "chrUnknown", False, False, "<aligned reads>", None, penalty_model,
+        cluster_groups=groups, joint_search=search)
+    return interval, _consensus_result((fits, clusters), groups, chrom)
+
+
+def learn_joint_penalty_dense(count_vecs, labels, **kwargs):
+    """The joint penalty learned from labels: joint_target_interval_dense's JointTargetInterval;
+    its .penalty is a float that joint_peaks_dense(joint_penalty=...) takes as it is."""
+    return joint_target_interval_dense(count_vecs, labels, **kwargs)[0]
+
+
+def learn_joint_penalty_reads(reads, labels, **kwargs):
+    """learn_joint_penalty_dense from aligned reads (joint_target_interval_reads)."""
+    return joint_target_interval_reads(reads, labels, **kwargs)[0]
 
 
 # ---- coverage features and learned penalties (additive; DESIGN.md section 13) ----------------

@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, joint, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, joint, joint_path, joint_labels, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -94,6 +94,9 @@
 #include "peak_clusters.h"
 /* one common peak per window for all members of a group: the level-by-level search */
 #include "joint_peaks.h"
+/* the joint peaks at many penalties in one call, and the label errors of every such model */
+#include "joint_path.h"
+#include "joint_labels.h"
 /* tests only: every form of the deterministic exp / log, element by element */
 #include "math_forms_probe.h"
 
@@ -137,6 +140,8 @@
 #include "peakseg_regions.h"
 #include "peakseg_clusters.h"
 #include "peakseg_joint.h"
+#include "peakseg_joint_path.h"
+#include "peakseg_joint_labels.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -188,7 +193,8 @@ extern "C" void peakseg_hip_problem_set_destroy(psd_problem_set *s) {
     if (e) (void)hipEventDestroy(e);
   for (auto &e : s->features.ev)
     if (e) (void)hipEventDestroy(e);
-  for (auto *ev : {s->regions.ev, s->clusters.ev, s->clusters.matrix.ev, s->joint.ev, s->joint.fold.ev})
+  for (auto *ev : {s->regions.ev, s->clusters.ev, s->clusters.matrix.ev, s->joint.ev, s->joint.fold.ev,
+                   s->joint_path.ev, s->joint_path.fold.ev, s->joint_labels.ev})
     for (int k = 0; k < 2; k++)
       if (ev[k]) (void)hipEventDestroy(ev[k]);
   if (s->stream) (void)hipStreamDestroy(s->stream);

@@ -2,34 +2,45 @@
  * penalty, the groups and the windows, the members' layout and the groups' common extents, the
  * room, the launches level by level (whose folds are regions_fold of peakseg_regions.h), the one
  * download of the head, and the download of the columns.  With no windows given the clusters of
- * peakseg_clusters.h are the windows. */
+ * peakseg_clusters.h are the windows.  joint_check_groups() and joint_run() also serve the path of many
+ * penalties (peakseg_joint_path.h; kernels: joint_path.h), which has a table of its own. */
 
 namespace {
 
-thread_local float g_joint_ms = 0.f;
+thread_local float g_joint_ms = 0.f, g_joint_path_ms = 0.f;
+
+/* the path's launches after its setup (peakseg_joint_path.h) */
+int joint_path_launches(psd_problem_set *s, JointTable &t, const psd::joint::Groups &groups,
+                        const psd::joint::Windows &win, int n_groups, long long windows,
+                        long long entries, int n_pen, const double *penalties, int max_levels,
+                        long long most_items, long long most_items_path);
 
 /* bytes of the call's tables by what they are counted in */
 constexpr unsigned long long JOINT_GROUP_BYTES = 4 + 4 * 8 + 2 * 8, JOINT_MEMBER_BYTES = 4,
                              JOINT_WINDOW_BYTES = 2 * 4 + 8 * 4 + 8,
-                             JOINT_ENTRY_BYTES = 8 + 8 + 4 + 4 + 8 + 3 * 4 * psd::joint::BINS;
+                             JOINT_ENTRY_BYTES = 8 + 8 + 4 + 4 + 8, JOINT_REGION_BYTES = 3 * 4;
 
-/* the bytes joint_room() would add to what the set holds */
+/* the bytes joint_room() would add to what the set holds; windows, entries: rows (of every
+ * penalty); regions: those of the level with most; carry: doubles (the path's level 0) */
 unsigned long long joint_room_bytes(const psd_problem_set *s, const JointTable &t, long long groups,
-                                    long long members, long long windows, long long entries) {
+                                    long long members, long long windows, long long entries,
+                                    long long regions, long long carry) {
   auto grow = [](long long have, long long need, unsigned long long each) {
     return need > have ? (unsigned long long)(need - have) * each : 0ull;
   };
-  unsigned long long more = regions_room_bytes(s, t.fold, entries * psd::joint::BINS);
+  unsigned long long more = regions_room_bytes(s, t.fold, regions);
   more += grow(t.group_capacity, groups + 1, JOINT_GROUP_BYTES);
   more += grow(t.member_capacity, members > 0 ? members : 1, JOINT_MEMBER_BYTES);
   more += grow(t.window_capacity, windows > 0 ? windows : 1, JOINT_WINDOW_BYTES);
   more += grow(t.entry_capacity, entries > 0 ? entries : 1, JOINT_ENTRY_BYTES);
+  more += grow(t.region_capacity, regions > 0 ? regions : 1, JOINT_REGION_BYTES);
+  more += grow(t.carry_capacity, carry, 8);
   if (!t.head) more += sizeof(psd::joint::Head);
   return more;
 }
 
 int joint_room(psd_problem_set *s, JointTable &t, long long groups, long long members,
-               long long windows, long long entries) {
+               long long windows, long long entries, long long regions, long long carry) {
   int st = 0;
   for (auto &e : t.ev)
     if (!e) HIP_TRY(hipEventCreate(&e));
@@ -64,37 +75,56 @@ int joint_room(psd_problem_set *s, JointTable &t, long long groups, long long me
   }
   if (entries > t.entry_capacity || !t.total) {
     const long long have = t.entry_capacity, need = entries > 0 ? entries : 1;
-    const long long slots = psd::joint::BINS;
     t.entry_capacity = 0;
     if ((st = label_room(s, t.total, have, need)) || (st = label_room(s, t.m_gain, have, need)) ||
         (st = label_room(s, t.m_up, have, need)) || (st = label_room(s, t.m_bases, have, need)) ||
-        (st = label_room(s, t.m_sum, have, need)) ||
-        (st = label_room(s, t.region_start, slots * have, slots * need)) ||
-        (st = label_room(s, t.region_end, slots * have, slots * need)) ||
-        (st = label_room(s, t.region_contig, slots * have, slots * need)))
+        (st = label_room(s, t.m_sum, have, need)))
       return st;
     t.entry_capacity = need;
   }
-  return regions_room(s, t.fold, entries * psd::joint::BINS);
+  if (regions > t.region_capacity || !t.region_start) {
+    const long long have = t.region_capacity, need = regions > 0 ? regions : 1;
+    t.region_capacity = 0;
+    if ((st = label_room(s, t.region_start, have, need)) ||
+        (st = label_room(s, t.region_end, have, need)) ||
+        (st = label_room(s, t.region_contig, have, need)))
+      return st;
+    t.region_capacity = need;
+  }
+  if (carry > t.carry_capacity) {
+    const long long have = t.carry_capacity;
+    t.carry_capacity = 0;
+    if ((st = label_room(s, t.carry, have, carry))) return st;
+    t.carry_capacity = carry;
+  }
+  return regions_room(s, t.fold, regions);
 }
 
 /* 0 or a status; the device is set, the groups and the shape of the windows have been checked.
- * n_windows == NULL: the clusters are the windows. */
-int joint_run(psd_problem_set *s, const int *first_chromStart, int n_groups, const int *group,
-              double penalty, const long long *n_windows, const int *const *window_start,
+ * n_windows == NULL: the clusters are the windows.  n_pen == 0: joint_peaks.h's kernels at
+ * `penalty`, into t = s->joint; n_pen >= 1: joint_path.h's at penalties[0 .. n_pen), into
+ * t = s->joint_path, every column penalty-major.  who: the call, for the messages. */
+int joint_run(psd_problem_set *s, JointTable &t, const char *who, const int *first_chromStart,
+              int n_groups, const int *group, double penalty, int n_pen, const double *penalties,
+              const long long *n_windows, const int *const *window_start,
               const int *const *window_end, int on_device, long long *windows_out,
               long long *members_out, long long *windows_total) {
   namespace jn = psd::joint;
+  namespace jp = psd::joint_path;
   namespace rg = psd::regions;
-  JointTable &t = s->joint;
+  const long long reps = n_pen > 0 ? n_pen : 1;
   const size_t ng = (size_t)n_groups;
   int st = 0;
   /* the members, group after group, in increasing problem index, and the groups' common extents */
   std::vector<int> member0(ng + 1, 0), member_contig;
   std::vector<long long> lo(ng + 1, 0), hi(ng + 1, -1);
   std::vector<std::vector<int>> of_group(ng);
+  if (n_pen > 0) t.problem_member.assign((size_t)s->n_problems, 0);
   for (int p = 0; p < s->n_problems; p++)
-    if (group[p] >= 0) of_group[(size_t)group[p]].push_back(p);
+    if (group[p] >= 0) {
+      if (n_pen > 0) t.problem_member[(size_t)p] = (int)of_group[(size_t)group[p]].size();
+      of_group[(size_t)group[p]].push_back(p);
+    }
   for (size_t g = 0; g < ng; g++) {
     bool any = false;
     for (int p : of_group[g]) {
@@ -136,23 +166,35 @@ int joint_run(psd_problem_set *s, const int *first_chromStart, int n_groups, con
   const long long windows = win_off[ng], entries = entry_off[ng];
   const long long members = (long long)member_contig.size();
   /* (a grid dimension times the workgroup size stays below 2^32; a workgroup per window) */
-  if ((entries * jn::BINS + jn::THREADS - 1) / jn::THREADS >= (1ll << 24) || windows >= (1ll << 31)) {
-    set_error("pack_joint_peaks: %lld windows and %lld entries of the matrix in one call", windows,
-              entries);
+  const long long most_slots = reps * jn::REFINE > jn::BINS ? reps * jn::REFINE : jn::BINS;
+  int most_members = 0;
+  for (size_t g = 0; g < ng; g++)
+    if (counts[g] > 0 && member0[g + 1] - member0[g] > most_members) most_members = member0[g + 1] - member0[g];
+  /* (level 0 of the path: groups of more than a slab of members keep their sums between slabs) */
+  int pen_t = 1;
+  while (pen_t < n_pen) pen_t <<= 1;
+  const long long carry = n_pen > 0 && most_members > jn::SLAB ? windows * pen_t * jn::MAX_CAND : 0;
+  if ((entries * most_slots + jn::THREADS - 1) / jn::THREADS >= (1ll << 24) || windows >= (1ll << 31) ||
+      (windows * reps + jn::THREADS - 1) / jn::THREADS >= (1ll << 24)) {
+    set_error("%s: %lld windows and %lld entries of the matrix in one call", who, windows, entries);
     return ERROR_REGION_ARGUMENTS;
   }
   /* does it fit?  asked before anything of it is allocated or written */
   {
-    const unsigned long long more = joint_room_bytes(s, t, n_groups, members, windows, entries);
+    const unsigned long long more = joint_room_bytes(s, t, n_groups, members, windows * reps,
+                                                     entries * reps, entries * most_slots, carry);
     size_t free_b = 0, total_b = 0;
     const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
     if ((s->max_bytes && s->bytes + more > s->max_bytes) || (known && more > (unsigned long long)free_b)) {
-      set_error("pack_joint_peaks: the tables of %lld windows and %lld entries need %llu more bytes, "
-                "which do not fit (free HBM / PEAKSEG_HIP_MAX_BYTES)", windows, entries, more);
+      set_error("%s: the tables of %lld windows and %lld entries need %llu more bytes, "
+                "which do not fit (free HBM / PEAKSEG_HIP_MAX_BYTES)", who, windows * reps,
+                entries * reps, more);
       return ERROR_DEVICE_MEMORY;
     }
   }
-  if ((st = joint_room(s, t, n_groups, members, windows, entries))) return st;
+  if ((st = joint_room(s, t, n_groups, members, windows * reps, entries * reps, entries * most_slots,
+                       carry)))
+    return st;
   /* given windows: where the caller has them, or the library's copy of host arrays (checked here;
    * setup_kernel checks what the host cannot see) */
   if (n_windows) {
@@ -168,7 +210,7 @@ int joint_run(psd_problem_set *s, const int *first_chromStart, int n_groups, con
       }
       for (long long i = 0; i < m; i++)
         if (window_start[g][i] >= window_end[g][i]) {
-          set_error("pack_joint_peaks: group %d: window %lld has start %d >= end %d", (int)g, i,
+          set_error("%s: group %d: window %lld has start %d >= end %d", who, (int)g, i,
                     window_start[g][i], window_end[g][i]);
           return ERROR_REGION_ARGUMENTS;
         }
@@ -190,7 +232,8 @@ int joint_run(psd_problem_set *s, const int *first_chromStart, int n_groups, con
   if (members > 0)
     HIP_TRY(hipMemcpy(t.member_contig, member_contig.data(), sizeof(int) * (size_t)members,
                       hipMemcpyHostToDevice));
-  g_joint_ms = 0.f;
+  float &ms = n_pen > 0 ? g_joint_path_ms : g_joint_ms;
+  ms = 0.f;
   *windows_total = windows;
   t.entries = entries;
   if (windows == 0) return 0;
@@ -211,6 +254,7 @@ int joint_run(psd_problem_set *s, const int *first_chromStart, int n_groups, con
     }
     most_items += counts[g] * tiles;
   }
+  const long long most_items_path = most_items * reps; /* (a piece per penalty) */
   jn::Groups groups;
   groups.member0 = t.member0;
   groups.win_off = t.win_off;
@@ -233,9 +277,15 @@ int joint_run(psd_problem_set *s, const int *first_chromStart, int n_groups, con
   if (on_device) HIP_TRY(hipStreamSynchronize((hipStream_t) nullptr));
   HIP_TRY(hipEventRecord(t.ev[0], s->stream));
   HIP_TRY(hipMemsetAsync(t.head, 0, sizeof(jn::Head), s->stream));
-  hipLaunchKernelGGL(jn::setup_kernel, dim3((unsigned)((windows + jn::THREADS - 1) / jn::THREADS)),
-                     dim3(jn::THREADS), 0, s->stream, groups, n_groups, windows, n_windows ? 0 : 1, win,
-                     t.head);
+  if (n_pen > 0)
+    hipLaunchKernelGGL(jp::setup_kernel<>,
+                       dim3((unsigned)((windows * reps + jn::THREADS - 1) / jn::THREADS)),
+                       dim3(jn::THREADS), 0, s->stream, groups, n_groups, windows, n_pen,
+                       n_windows ? 0 : 1, win, t.head);
+  else
+    hipLaunchKernelGGL(jn::setup_kernel, dim3((unsigned)((windows + jn::THREADS - 1) / jn::THREADS)),
+                       dim3(jn::THREADS), 0, s->stream, groups, n_groups, windows, n_windows ? 0 : 1,
+                       win, t.head);
   HIP_TRY(hipGetLastError());
   jn::Head head;
   HIP_TRY(hipMemcpyAsync(&head, t.head, sizeof head, hipMemcpyDeviceToHost, s->stream));
@@ -244,8 +294,17 @@ int joint_run(psd_problem_set *s, const int *first_chromStart, int n_groups, con
     const long long w = (long long)~head.check;
     size_t g = 0;
     while (g + 1 < ng && win_off[g + 1] <= w) g++;
-    set_error("pack_joint_peaks: group %d: window %lld has start >= end", (int)g, w - win_off[g]);
+    set_error("%s: group %d: window %lld has start >= end", who, (int)g, w - win_off[g]);
     return ERROR_REGION_ARGUMENTS;
+  }
+  if (n_pen > 0) {
+    if ((st = joint_path_launches(s, t, groups, win, n_groups, windows, entries, n_pen, penalties,
+                                  head.max_levels, most_items, most_items_path)))
+      return st;
+    HIP_TRY(hipEventRecord(t.ev[1], s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+    return 0;
   }
   auto pass = [&](int slots) -> int {
     const long long n = entries * slots;
@@ -276,6 +335,38 @@ int joint_run(psd_problem_set *s, const int *first_chromStart, int n_groups, con
   return 0;
 }
 
+/* the checks of the groups and of the windows' shape: 0 or what the call returns */
+long long joint_check_groups(const psd_problem_set *s, const char *who, int n_groups, const int *group,
+                             const long long *n_windows, const int *const *window_start,
+                             const int *const *window_end, int windows_on_device) {
+  if (n_groups < 0 || (!group && s->n_problems > 0)) {
+    set_error("%s: %d groups%s", who, n_groups, group ? "" : " and no group array");
+    return -ERROR_REGION_ARGUMENTS;
+  }
+  for (int p = 0; p < s->n_problems; p++)
+    if (group[p] < -1 || group[p] >= n_groups) {
+      set_error("%s: problem %d is in group %d, outside -1 .. %d", who, p, group[p], n_groups - 1);
+      return -ERROR_REGION_ARGUMENTS;
+    }
+  for (int g = 0; g < n_groups && n_windows; g++) {
+    if (n_windows[g] < 0) {
+      set_error("%s: group %d has %lld windows", who, g, n_windows[g]);
+      return -ERROR_REGION_ARGUMENTS;
+    }
+    if (n_windows[g] == 0) continue;
+    const int *const *arrays[2] = {window_start, window_end};
+    for (int j = 0; j < 2; j++) {
+      const int *a = arrays[j] ? arrays[j][g] : nullptr;
+      if (!a || (windows_on_device && ((unsigned long long)a & 3ull))) {
+        set_error("%s: group %d: the window %s array is %s", who, g, j ? "end" : "start",
+                  a ? "at a device address that is no multiple of 4" : "NULL");
+        return -ERROR_REGION_ARGUMENTS;
+      }
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" long long peakseg_hip_problem_set_pack_joint_peaks(
@@ -298,36 +389,13 @@ extern "C" long long peakseg_hip_problem_set_pack_joint_peaks(
     set_error("pack_joint_peaks: the penalty %g is negative or not a number", penalty);
     return -ERROR_REGION_ARGUMENTS;
   }
-  if (n_groups < 0 || (!group && s->n_problems > 0)) {
-    set_error("pack_joint_peaks: %d groups%s", n_groups, group ? "" : " and no group array");
-    return -ERROR_REGION_ARGUMENTS;
-  }
-  for (int p = 0; p < s->n_problems; p++)
-    if (group[p] < -1 || group[p] >= n_groups) {
-      set_error("pack_joint_peaks: problem %d is in group %d, outside -1 .. %d", p, group[p],
-                n_groups - 1);
-      return -ERROR_REGION_ARGUMENTS;
-    }
-  for (int g = 0; g < n_groups && n_windows; g++) {
-    if (n_windows[g] < 0) {
-      set_error("pack_joint_peaks: group %d has %lld windows", g, n_windows[g]);
-      return -ERROR_REGION_ARGUMENTS;
-    }
-    if (n_windows[g] == 0) continue;
-    const int *const *arrays[2] = {window_start, window_end};
-    for (int j = 0; j < 2; j++) {
-      const int *a = arrays[j] ? arrays[j][g] : nullptr;
-      if (!a || (windows_on_device && ((unsigned long long)a & 3ull))) {
-        set_error("pack_joint_peaks: group %d: the window %s array is %s", g, j ? "end" : "start",
-                  a ? "at a device address that is no multiple of 4" : "NULL");
-        return -ERROR_REGION_ARGUMENTS;
-      }
-    }
-  }
+  if (const long long bad = joint_check_groups(s, "pack_joint_peaks", n_groups, group, n_windows,
+                                               window_start, window_end, windows_on_device))
+    return bad;
   long long total = 0;
-  const int st = joint_run(s, first_chromStart, n_groups, group, penalty, n_windows, window_start,
-                           window_end, n_windows ? windows_on_device : 0, windows_out, members_out,
-                           &total);
+  const int st = joint_run(s, s->joint, "pack_joint_peaks", first_chromStart, n_groups, group, penalty,
+                           0, nullptr, n_windows, window_start, window_end,
+                           n_windows ? windows_on_device : 0, windows_out, members_out, &total);
   if (st) return st == ERROR_REGION_ARGUMENTS || st == ERROR_DEVICE_MEMORY ? -st : -1;
   const JointTable &t = s->joint;
   s->joint.windows = total;

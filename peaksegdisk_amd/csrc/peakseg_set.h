@@ -125,7 +125,10 @@ struct ClusterTable {
 
 /* What peakseg_hip_problem_set_pack_joint_peaks keeps (peakseg_joint.h): the groups and members of a
  * call, the windows with their peaks, the regions of a level and their fold, and the matrix.  Every
- * array grows to what the largest call so far needed. */
+ * array grows to what the largest call so far needed.  pack_joint_path keeps a table of its own of
+ * the same kind, with a row per (penalty, window) and per (penalty, entry), and what
+ * pack_joint_label_errors needs of the call: the penalties' number and every problem's group and
+ * place among its members. */
 struct JointTable {
   int *member0 = nullptr;                                        /* groups + 1 */
   long long *win_off = nullptr, *entry_off = nullptr, *lo = nullptr, *hi = nullptr; /* groups + 1 */
@@ -143,10 +146,33 @@ struct JointTable {
   double *m_gain = nullptr;
   int *m_up = nullptr, *m_bases = nullptr;
   long long *m_sum = nullptr;
-  int *region_start = nullptr, *region_end = nullptr, *region_contig = nullptr; /* 64 per entry */
   long long entry_capacity = 0;
+  int *region_start = nullptr, *region_end = nullptr, *region_contig = nullptr; /* per region of a level */
+  long long region_capacity = 0;
   RegionTable fold;     /* the fold of a level's regions */
   long long windows = -1, entries = -1; /* of the last call (-1: nothing packed) */
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  /* the path only */
+  double *carry = nullptr;               /* level 0's sums between slabs of members */
+  long long carry_capacity = 0;
+  int penalties = 0, groups = 0;         /* of the last call */
+  std::vector<int> problem_group, problem_member; /* per problem: its group (-1: none), its place in it */
+};
+
+/* What peakseg_hip_problem_set_pack_joint_label_errors keeps (peakseg_joint_labels.h). */
+struct JointLabelTable {
+  psd::joint_labels::Problem *d_problems = nullptr; /* per problem */
+  long long *d_lab_off = nullptr;                   /* problems + 1 */
+  unsigned long long *d_check = nullptr;            /* per problem */
+  int *d_labels = nullptr;                          /* 3 x labels (host arrays only) */
+  long long label_capacity = 0;
+  int *count = nullptr, *fp = nullptr, *fn = nullptr; /* per (penalty, label) */
+  long long row_capacity = 0;
+  int *totals = nullptr;                            /* TOTALS per (penalty, problem) */
+  long long total_capacity = 0;
+  long long *model = nullptr;                       /* TOTALS per penalty (MAX_PENALTIES of them) */
+  long long labels = -1;                            /* of the last call (-1: nothing packed) */
+  int penalties = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
@@ -217,6 +243,8 @@ struct psd_problem_set {
   RegionTable regions; /* (sets made from dense counts) */
   ClusterTable clusters; /* (sets made from dense counts) */
   JointTable joint; /* (sets made from dense counts) */
+  JointTable joint_path; /* (sets made from dense counts) */
+  JointLabelTable joint_labels; /* (sets made from dense counts) */
 
   /* Sets made from dense counts (peakseg_hip_problem_set_create_dense): run_end[] next to count[]
    * and weight[], the sum of each contig's counts, and which contigs are constant.  Their trivial

@@ -59,6 +59,27 @@ def annotation_codes(annotation, what="labels"):
     return codes
 
 
+_JOINT_DTYPES = (np.int32,) * 4 + (np.float64, np.int32, np.int32, np.float64, np.int32, np.int64,
+                                   np.int32)  # the eleven columns of joint_peaks() and joint_path()
+
+
+def _joint_groups(group, n_groups, k, m, w_off, e_off, cols):
+    """the eleven columns of one joint model -> the list over groups that joint_peaks() returns"""
+    import pandas as pd
+    result = []
+    for g in range(n_groups):
+        rows = slice(int(w_off[g]), int(w_off[g + 1]))
+        cells = slice(int(e_off[g]), int(e_off[g + 1]))
+        entry = {"members": np.flatnonzero(group == g),
+                 "joint": pd.DataFrame({name: cols[j][rows] for j, name in enumerate(
+                     ("windowStart", "windowEnd", "peakStart", "peakEnd", "objective",
+                      "samples_up", "levels"))})}
+        for j, name in enumerate(("gain", "up", "sum", "bases")):
+            entry[name] = cols[7 + j][cells].reshape(int(k[g]), int(m[g]))
+        result.append(entry)
+    return result
+
+
 def read_labels_bed(path):
     """A labels.bed file as the reference's tests write it -- chrom, chromStart, chromEnd,
     annotation, separated by white space -- as (the `labels` entry of one contig for
@@ -643,20 +664,56 @@ class ProblemSet:
         entries[g]:entries[g + 1], window-major); they are valid until the next solve(), the next
         joint_peaks() or close().  A window with start >= end, and a penalty that is negative or
         NaN, raise RuntimeError with .status 22."""
+        group, n_groups, first, given, on_device = self._joint_arguments(
+            "joint_peaks", groups, windows, first_chromStart)
+        room = max(n_groups, 1)
+        k = np.zeros(room, dtype=np.int64)
+        m = np.zeros(room, dtype=np.int64)
+        out = [ctypes.c_void_p() for _ in range(11)]
+        total = self._lib.peakseg_hip_problem_set_pack_joint_peaks(
+            self._h, first.ctypes.data if first is not None else None, n_groups, group.ctypes.data,
+            float(penalty), *([ctypes.addressof(a) for a in given[:3]] if given else [None, None, None]),
+            on_device, k.ctypes.data, m.ctypes.data, *[ctypes.byref(q) for q in out])
+        del given  # (the library holds no reference to the caller's buffers after the call)
+        if total < 0:
+            self._raise_status("pack_joint_peaks", total)
+        total = int(total)
+        k, m = k[:n_groups], m[:n_groups]
+        w_off = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
+        e_off = np.concatenate([[0], np.cumsum(k * m)]).astype(np.int64)
+        entries = int(e_off[-1])
+        sizes = (total,) * 7 + (entries,) * 4
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            return (w_off, e_off) + tuple(device_array(q.value or 0, n, dt, dev)
+                                          for q, n, dt in zip(out, sizes, _JOINT_DTYPES))
+        cols = [np.empty(n, dtype=dt) for n, dt in zip(sizes, _JOINT_DTYPES)]
+        if self._lib.peakseg_hip_problem_set_packed_joint_peaks_download(
+                self._h, *[a.ctypes.data for a in cols]) != 0:
+            raise RuntimeError("packed_joint_peaks_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        return _joint_groups(group, n_groups, k, m, w_off, e_off, cols)
+
+    def _joint_arguments(self, who, groups, windows, first_chromStart):
+        """the arguments joint_peaks() and joint_path() share -> (group int32[], n_groups,
+        first_chromStart or None, the three ctypes tables of given windows followed by what keeps
+        their memory alive -- [] for windows=None --, 1 for windows in device memory)"""
         group = np.ascontiguousarray(groups, dtype=np.int32) if len(groups) else np.zeros(0, np.int32)
         if group.shape != (len(self.problems),):
-            raise ValueError("joint_peaks: one group per problem (%d values, %d problems)"
-                             % (group.size, len(self.problems)))
+            raise ValueError("%s: one group per problem (%d values, %d problems)"
+                             % (who, group.size, len(self.problems)))
         if not np.array_equal(group, np.asarray(groups)):
-            raise ValueError("joint_peaks: groups must be integers")
+            raise ValueError("%s: groups must be integers" % who)
         n_groups = int(group.max()) + 1 if group.size and group.max() >= 0 else 0
         first = self._first_chromStart(first_chromStart)
         keep, sides, lengths = [], [], None
         ptrs = ([], [])
         if windows is not None:
             if len(windows) != n_groups:
-                raise ValueError("joint_peaks: one entry of windows per group (%d entries, %d groups)"
-                                 % (len(windows), n_groups))
+                raise ValueError("%s: one entry of windows per group (%d entries, %d groups)"
+                                 % (who, len(windows), n_groups))
             lengths = []
             for g, entry in enumerate(windows):
                 if entry is None or len(entry) == 0:
@@ -665,14 +722,14 @@ class ProblemSet:
                         q.append(0)
                     continue
                 if len(entry) != 2:
-                    raise ValueError("joint_peaks: the windows of group %d are not (start, end)" % g)
+                    raise ValueError("%s: the windows of group %d are not (start, end)" % (who, g))
                 n = None
                 for j in range(2):
                     ptr, m, side, ref = _dense_pointer(
-                        g, entry[j], self.device, "joint_peaks: group %d window " + ("start", "end")[j])
+                        g, entry[j], self.device, who + ": group %d window " + ("start", "end")[j])
                     if n is not None and m != n:
-                        raise ValueError("joint_peaks: group %d has %d window starts and %d ends"
-                                         % (g, n, m))
+                        raise ValueError("%s: group %d has %d window starts and %d ends"
+                                         % (who, g, n, m))
                     n = m
                     keep.append(ref)
                     sides.append((side, g))
@@ -680,55 +737,148 @@ class ProblemSet:
                 lengths.append(n)
             for side, g in sides:
                 if side != sides[0][0]:
-                    raise ValueError("joint_peaks: group %d is in %s memory but group %d is in %s "
-                                     "memory; one call takes one kind" % (g, side, sides[0][1], sides[0][0]))
+                    raise ValueError("%s: group %d is in %s memory but group %d is in %s "
+                                     "memory; one call takes one kind"
+                                     % (who, g, side, sides[0][1], sides[0][0]))
+        room = max(n_groups, 1)
+        given = []
+        if lengths is not None:
+            given = [(ctypes.c_longlong * room)(*lengths)] + [(ctypes.c_void_p * room)(*q) for q in ptrs]
+            given.append(keep)
+        return group, n_groups, first, given, 1 if sides and sides[0][0] == "device" else 0
+
+    def joint_path(self, groups, penalties, windows=None, first_chromStart=None, torch_device=None):
+        """joint_peaks() at every one of `penalties` in one call
+        (peakseg_hip_problem_set_pack_joint_path): what does not depend on the penalty -- the
+        level-0 bins, their fold, and the feasibility and the gain of every (candidate, member) --
+        is computed once per window, and the number of launches is that of one joint_peaks().
+        penalties: 1 to peakseg_hip_joint_path_max_penalties() (16) numbers >= 0 in any order,
+        repeats and +inf allowed; the other arguments as joint_peaks().  Without torch_device: a
+        list over penalties of exactly what joint_peaks() returns at that penalty, bit for bit.
+        With torch_device: (windows int64 numpy[n_groups + 1], entries int64 numpy[n_groups + 1],
+        and joint_peaks()'s eleven tensors with a leading penalty dimension: [n_penalties, windows]
+        and [n_penalties, entries]), aliases of the library's buffers, valid until the next
+        solve(), the next joint_path() or close() -- a joint_peaks() does not touch them, nor the
+        other way round.  The penalties' number out of range, and a negative or NaN penalty (named
+        by its index), raise RuntimeError with .status 22."""
+        group, n_groups, first, given, on_device = self._joint_arguments(
+            "joint_path", groups, windows, first_chromStart)
+        pens = np.ascontiguousarray(penalties, dtype=np.float64).reshape(-1)
+        n_pen = int(pens.size)
         room = max(n_groups, 1)
         k = np.zeros(room, dtype=np.int64)
         m = np.zeros(room, dtype=np.int64)
         out = [ctypes.c_void_p() for _ in range(11)]
-        given = []
-        if lengths is not None:
-            given = [(ctypes.c_longlong * room)(*lengths)] + [(ctypes.c_void_p * room)(*q) for q in ptrs]
-        total = self._lib.peakseg_hip_problem_set_pack_joint_peaks(
+        total = self._lib.peakseg_hip_problem_set_pack_joint_path(
             self._h, first.ctypes.data if first is not None else None, n_groups, group.ctypes.data,
-            float(penalty), *([ctypes.addressof(a) for a in given] if given else [None, None, None]),
-            1 if sides and sides[0][0] == "device" else 0, k.ctypes.data, m.ctypes.data,
-            *[ctypes.byref(q) for q in out])
-        del keep  # (the library holds no reference to the caller's buffers after the call)
+            n_pen, pens.ctypes.data,
+            *([ctypes.addressof(a) for a in given[:3]] if given else [None, None, None]),
+            on_device, k.ctypes.data, m.ctypes.data, *[ctypes.byref(q) for q in out])
+        del given  # (the library holds no reference to the caller's buffers after the call)
         if total < 0:
-            self._raise_status("pack_joint_peaks", total)
+            self._raise_status("pack_joint_path", total)
         total = int(total)
+        self._joint_path_penalties = n_pen
         k, m = k[:n_groups], m[:n_groups]
         w_off = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
         e_off = np.concatenate([[0], np.cumsum(k * m)]).astype(np.int64)
         entries = int(e_off[-1])
-        dtypes = (np.int32,) * 4 + (np.float64, np.int32, np.int32, np.float64, np.int32, np.int64,
-                                    np.int32)
         sizes = (total,) * 7 + (entries,) * 4
         if torch_device is not None:
             import torch
             from .parallel import device_array
             dev = torch.device(torch_device)
-            return (w_off, e_off) + tuple(device_array(q.value or 0, n, dt, dev)
-                                          for q, n, dt in zip(out, sizes, dtypes))
-        cols = [np.empty(n, dtype=dt) for n, dt in zip(sizes, dtypes)]
-        if self._lib.peakseg_hip_problem_set_packed_joint_peaks_download(
+            return (w_off, e_off) + tuple(
+                device_array(q.value or 0, n_pen * n, dt, dev).view(n_pen, n)
+                for q, n, dt in zip(out, sizes, _JOINT_DTYPES))
+        cols = [np.empty(n_pen * n, dtype=dt) for n, dt in zip(sizes, _JOINT_DTYPES)]
+        if self._lib.peakseg_hip_problem_set_packed_joint_path_download(
                 self._h, *[a.ctypes.data for a in cols]) != 0:
-            raise RuntimeError("packed_joint_peaks_download: %s"
+            raise RuntimeError("packed_joint_path_download: %s"
                                % self._lib.peakseg_hip_last_error().decode())
-        import pandas as pd
-        result = []
-        for g in range(n_groups):
-            rows = slice(int(w_off[g]), int(w_off[g + 1]))
-            cells = slice(int(e_off[g]), int(e_off[g + 1]))
-            entry = {"members": np.flatnonzero(group == g),
-                     "joint": pd.DataFrame({name: cols[j][rows] for j, name in enumerate(
-                         ("windowStart", "windowEnd", "peakStart", "peakEnd", "objective",
-                          "samples_up", "levels"))})}
-            for j, name in enumerate(("gain", "up", "sum", "bases")):
-                entry[name] = cols[7 + j][cells].reshape(int(k[g]), int(m[g]))
-            result.append(entry)
-        return result
+        return [_joint_groups(group, n_groups, k, m, w_off, e_off,
+                              [a[p * n:(p + 1) * n] for a, n in zip(cols, sizes)])
+                for p in range(n_pen)]
+
+    def joint_label_errors(self, labels, torch_device=None):
+        """The label errors of every model of the last joint_path(), counted on the device
+        (peakseg_hip_problem_set_pack_joint_label_errors; include/peaksegdisk_hip.h has the
+        definitions).  labels: a list over PROBLEMS of (chromStart, chromEnd, annotation) as
+        label_errors() takes them per contig, in the genomic coordinates the joint peaks are in; an
+        empty entry (or None) for a problem without labels.  The peaks of a problem in a model are
+        the joint peaks of its group's windows at which it is up.  Returns (model_totals int64
+        [n_penalties, 5], problem_totals int32 [n_penalties, n_problems, 5], rows): the totals are
+        errors, fp, fn, possible_fp, possible_fn, and rows[p][q] is the (count, fp, fn) int32
+        arrays of problem q's labels in model p.  With torch_device the totals and the three
+        columns ([n_penalties, labels], problem after problem) are tensors that alias the library's
+        buffers, as (offsets int64 numpy[n_problems + 1], count, fp, fn, problem_totals,
+        model_totals), valid until the next joint_path(), joint_label_errors() or close()."""
+        k = len(self.problems)
+        if len(labels) != k:
+            raise ValueError("joint_label_errors: one entry per problem (%d entries, %d problems)"
+                             % (len(labels), k))
+        names = ("chromStart", "chromEnd", "annotation")
+        keep, sides, lengths = [], [], []
+        ptrs = ([], [], [])
+        for q, entry in enumerate(labels):
+            if entry is None or len(entry) == 0:
+                lengths.append(0)
+                for col in ptrs:
+                    col.append(0)
+                continue
+            if len(entry) != 3:
+                raise ValueError("joint_label_errors: problem %d is not (chromStart, chromEnd, "
+                                 "annotation)" % q)
+            entry = list(entry)
+            entry[2] = annotation_codes(entry[2], "joint_label_errors: problem %d" % q)
+            n = None
+            for j in range(3):
+                ptr, m, side, ref = _dense_pointer(q, entry[j], self.device,
+                                                   "joint_label_errors: problem %d " + names[j])
+                if n is not None and m != n:
+                    raise ValueError("joint_label_errors: problem %d has %d chromStart and %d %s"
+                                     % (q, n, m, names[j]))
+                n = m
+                keep.append(ref)
+                sides.append((side, q))
+                ptrs[j].append(ptr if m else 0)
+            lengths.append(n)
+        for side, q in sides:
+            if side != sides[0][0]:
+                raise ValueError("joint_label_errors: problem %d is in %s memory but problem %d is "
+                                 "in %s memory; one call takes one kind"
+                                 % (q, side, sides[0][1], sides[0][0]))
+        room = max(k, 1)
+        out = [ctypes.c_void_p() for _ in range(5)]
+        total = self._lib.peakseg_hip_problem_set_pack_joint_label_errors(
+            self._h, (ctypes.c_longlong * room)(*lengths),
+            *[(ctypes.c_void_p * room)(*col) for col in ptrs],
+            1 if sides and sides[0][0] == "device" else 0, *[ctypes.byref(q) for q in out])
+        del keep  # (the library holds no reference to the caller's buffers after the call)
+        if total < 0:
+            self._raise_status("pack_joint_label_errors", total)
+        total = int(total)
+        offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        n_pen = self._joint_path_penalties       # (the call succeeded: a path is packed)
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            cols = tuple(device_array(q.value or 0, n_pen * total, np.int32, dev).view(n_pen, total)
+                         for q in out[:3])
+            return (offs,) + cols + (
+                device_array(out[3].value or 0, n_pen * k * 5, np.int32, dev).view(n_pen, k, 5),
+                device_array(out[4].value or 0, n_pen * 5, np.int64, dev).view(n_pen, 5))
+        cols = [np.empty(n_pen * total, dtype=np.int32) for _ in range(3)]
+        totals = np.empty((n_pen, k, 5), dtype=np.int32)
+        model = np.empty((n_pen, 5), dtype=np.int64)
+        if self._lib.peakseg_hip_problem_set_packed_joint_label_errors_download(
+                self._h, *[a.ctypes.data for a in cols], totals.ctypes.data, model.ctypes.data) != 0:
+            raise RuntimeError("packed_joint_label_errors_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        rows = [[tuple(a[p * total + offs[q]:p * total + offs[q + 1]] for a in cols)
+                 for q in range(k)] for p in range(n_pen)]
+        return model, totals, rows
 
     def _coverage_stats(self, ranks, torch_device=None):
         """one peakseg_hip_problem_set_pack_coverage_stats: ranks int64 [n_contigs, k], k at most
