@@ -18,6 +18,9 @@ margins of the same kind, for the same reason:
     integer test) or has gain - penalty < -4 E;
   - `up` is compared for equality, so every member feasible at the final peak has
     |gain - penalty| > 4 E."""
+import collections
+import hashlib
+
 import numpy as np
 
 BINS = 64
@@ -41,6 +44,14 @@ def _above(a, la, b, lb):
     return np.array([int(x) * int(l) > int(y) * int(k) for x, l, y, k in zip(a, la, b, lb)], bool)
 
 
+# What does not depend on the penalty -- per member its gain, feasibility, S2 and share of E at a
+# set of candidates -- is kept for the last few (members' counts in the window, candidates): the
+# tests of the joint path ask for the same window at up to 16 penalties in a row.  The key is the
+# content, so a hit returns what the computation would.
+_KEPT = collections.OrderedDict()
+_KEEP = 8
+
+
 class _Window:
     def __init__(self, vectors, firsts, ws, we, penalty, real):
         self.ws, self.we, self.penalty, self.real = ws, we, penalty, real
@@ -48,15 +59,17 @@ class _Window:
         for v, first in zip(vectors, firsts):
             part = np.asarray(v[ws - first:we - first], dtype=np.int64)
             self.cums.append(np.concatenate([[0], np.cumsum(part, dtype=np.int64)]))
+        digest = hashlib.sha256(b"".join(c.tobytes() for c in self.cums)).digest()
+        self.key = (digest, len(self.cums), ws, we, np.dtype(real).str)
 
-    def evaluate(self, s, e):
-        """candidates s[], e[] (int64) -> G[], E[], worst slack of a feasible member[], and per
-        member (gain[], feasible[], S2[])"""
+    def members_at(self, s, e):
+        """candidates s[], e[] (int64) -> per member (gain[], feasible[], S2[], its share of E[])"""
+        key = self.key + (s.tobytes(), e.tobytes())
+        if key in _KEPT:
+            _KEPT.move_to_end(key)
+            return _KEPT[key]
         real, ws, we = self.real, self.ws, self.we
         l1, l2, l3 = s - ws, e - s, we - e
-        G = np.zeros(len(s), real)
-        E = np.zeros(len(s), real)
-        slack = np.full(len(s), -np.inf, real)
         members = []
         for cum in self.cums:
             T = cum[-1]
@@ -67,9 +80,25 @@ class _Window:
             t1, t2, t3 = _term(s1, l1, real), _term(s2, l2, real), _term(s3, l3, real)
             t4 = _term(np.array([T]), np.array([we - ws]), real)[0]
             gain = ((t1 + t2) + t3) - t4
+            share = real(2.0 ** -50) * (real(T) + abs(t1) + abs(t2) + abs(t3) + abs(t4))
+            members.append((gain, ok, s2, share))
+        _KEPT[key] = members
+        while len(_KEPT) > _KEEP:
+            _KEPT.popitem(last=False)
+        return members
+
+    def evaluate(self, s, e):
+        """candidates s[], e[] (int64) -> G[], E[], worst slack of a feasible member[], and per
+        member (gain[], feasible[], S2[])"""
+        real = self.real
+        G = np.zeros(len(s), real)
+        E = np.zeros(len(s), real)
+        slack = np.full(len(s), -np.inf, real)
+        members = []
+        for gain, ok, s2, share in self.members_at(s, e):
             more = gain - real(self.penalty)
             G = G + np.where(ok & (more > 0), more, real(0))
-            E = E + real(2.0 ** -50) * (real(T) + abs(t1) + abs(t2) + abs(t3) + abs(t4))
+            E = E + share
             slack = np.where(ok, np.maximum(slack, more), slack)
             members.append((gain, ok, s2))
         return G, E, slack, members

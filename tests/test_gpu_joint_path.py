@@ -80,10 +80,10 @@ def run_path(psd, wrap, vectors, firsts, groups, windows, penalties, what="", re
     finally:
         pset.close()
     if ref:
-        for p, penalty in enumerate(penalties):
-            for g, entry in enumerate(models[p]):
-                members = [q for q in range(len(groups)) if groups[q] == g]
-                check_group(entry, [vectors[q] for q in members], [firsts[q] for q in members],
+        for g in range(len(windows)):     # (a group at all its penalties: the yardstick keeps what
+            members = [q for q in range(len(groups)) if groups[q] == g]    # they have in common)
+            for p, penalty in enumerate(penalties):
+                check_group(models[p][g], [vectors[q] for q in members], [firsts[q] for q in members],
                             windows[g], penalty, "%s penalty %g group %d" % (what, penalty, g))
     return models
 
@@ -168,17 +168,33 @@ def scenario_n_penalties(psd, wrap):
         capped.close()
 
 
+def member_groups(kinds_of_groups):
+    """a group per entry (size, {member: kind}): member_vector(k, kind), "peak" where none is
+    given -> (vectors, groups); the contigs start at 1000"""
+    vectors, groups = [], []
+    for g, (size, kinds) in enumerate(kinds_of_groups):
+        for k in range(size):
+            vectors.append(member_vector(k, kinds.get(k, "peak")))
+            groups.append(g)
+    return vectors, groups
+
+
+MEMBER_SIZES = [1, 64, 65, 130]
+
+
+def members_set():
+    """the 260 problems of scenario_members: in the group of 65 an all-zero member, an infeasible
+    one and a weak one"""
+    return member_groups([(size, {3: "zero", 40: "dip", 64: "weak"} if size == 65 else {})
+                          for size in MEMBER_SIZES])
+
+
 def scenario_members(psd, wrap):
     """groups of 1, 64, 65 and 130 members with three penalties each: the accumulators of several
     penalties across the boundaries of the slabs of 64 members (and of the smaller slabs of the
     later levels); in the group of 65 an all-zero member, an infeasible one and a weak one"""
-    sizes = [1, 64, 65, 130]
-    vectors, groups = [], []
-    for g, size in enumerate(sizes):
-        for k in range(size):
-            kind = {3: "zero", 40: "dip", 64: "weak"}.get(k, "peak") if size == 65 else "peak"
-            vectors.append(member_vector(k, kind))
-            groups.append(g)
+    sizes = MEMBER_SIZES
+    vectors, groups = members_set()
     firsts = [1000] * len(vectors)
     windows = [[(1020, 1180)]] * len(sizes)
     models = run_path(psd, wrap, vectors, firsts, groups, windows, [25.0, 1e9, 0.0], "members")
@@ -291,6 +307,134 @@ def scenario_independence(psd, wrap):
         pset.close()
 
 
+SLAB = 64                                             # members of a level-0 slab, of any instance
+LATER_SLAB = {1: 64, 2: 64, 4: 57, 8: 28, 16: 14}     # members of a later level's slab, by instance
+# 16 penalties, every prefix of which is a call: some members do not reach 25, no window has a
+# peak at 1e9 (it idles between penalties that refine), 0, and values every strong member exceeds
+LADDER = [25.0, 1e9, 0.0] + [30.0 + 7.0 * k for k in range(13)]
+
+
+def instance_of(n_pen):
+    """the accumulators the kernels are compiled for: the next power of two"""
+    width = 1
+    while width < n_pen:
+        width *= 2
+    return width
+
+
+def widths_case(n_pen):
+    """the groups of scenario_penalty_widths_past_slabs for a call of n_pen penalties ->
+    [(size, {member: kind})]"""
+    later = LATER_SLAB[instance_of(n_pen)]
+    # on a later level's slab line, one past it (the zero member the last of the first slab, the
+    # weak one the first of the second), and one past level 0's (for 1 and 2 penalties the same)
+    cases = [(later, {}), (later + 1, {1: "dip", later - 1: "zero", later: "weak"})]
+    if later + 1 != SLAB + 1:
+        cases.append((SLAB + 1, {3: "dip", SLAB - 1: "zero", SLAB: "weak"}))
+    if n_pen in (8, 16):
+        cases.append((2 * SLAB + 1, {SLAB - 1: "zero", SLAB: "dip", 2 * SLAB: "weak"}))
+    return cases
+
+
+def scenario_penalty_widths_past_slabs(psd, wrap):
+    """every instance of search0_kernel and refine_kernel (1, 2, 4, 8 and 16 accumulators), once
+    with as many penalties as accumulators and once with padded ones, on groups on and one past
+    the slab line of the later levels (64, 64, 57, 28 and 14 members), one past level 0's (65: the
+    carry in HBM) and, for 8 and 16 penalties, of three level-0 slabs (129); two windows per group
+    (W = 160 and 120: three levels and two), so the carry of a window is not the group's"""
+    windows = [(1020, 1180), (1030, 1150)]
+    seen = set()
+    for n_pen in (1, 2, 3, 4, 5, 8, 9, 16):
+        width, cases = instance_of(n_pen), widths_case(n_pen)
+        later = LATER_SLAB[width]
+        sizes = [size for size, _ in cases]
+        assert width >= n_pen > width // 2 and later in sizes and later + 1 in sizes
+        assert SLAB + 1 in sizes and all(size > 2 * SLAB for size in sizes[3:])
+        if n_pen in (8, 16):
+            assert -(-sizes[3] // SLAB) == 3 and -(-sizes[3] // later) == {8: 5, 16: 10}[n_pen]
+        seen.add((width, n_pen == width))
+        penalties = LADDER[:n_pen]
+        vectors, groups = member_groups(cases)
+        models = run_path(psd, wrap, vectors, [1000] * len(vectors), groups,
+                          [windows] * len(cases), penalties, "%d penalties" % n_pen)
+        for penalty, model in zip(penalties, models):
+            for (size, kinds), entry in zip(cases, model):
+                frame = entry["joint"]
+                if penalty == 1e9:
+                    assert frame["peakStart"].tolist() == [-1, -1] and not entry["up"].any()
+                    assert frame["levels"].tolist() == [0, 0]
+                    continue
+                assert frame["peakStart"].tolist() == [1070, 1070], (n_pen, penalty, size)
+                assert frame["peakEnd"].tolist() == [1110, 1110] and frame["levels"].tolist() == [3, 2]
+                want = np.ones(size, np.int32)
+                for k, kind in kinds.items():
+                    want[k] = kind == "weak" and penalty == 0.0
+                assert entry["up"].tolist() == [want.tolist()] * 2, (n_pen, penalty, size)
+    assert seen == {(w, full) for w in LATER_SLAB for full in (True, False)} - {(1, False), (2, False)}
+
+
+MANY_STRONG = {0: 9, 35: 10, 69: 11}                  # member: the height of its bump [64, 96)
+MANY_PENALTIES = [100.0, 0.0, 1e4, 150.0, 1.5, INF, 60.0, 200.0, 46.0, 80.0, 20.0, 120.0, 240.0,
+                  175.0, 300.0, 110.0]
+
+
+def scenario_moving_peak_many_members(psd, wrap):
+    """the moving peak in a group of 70 members at 16 penalties: three strong members with a bump
+    [64, 96), one of them in the second level-0 slab, and 67 weak ones with a bump [256, 288).  The
+    small penalties end on the weak members' peak, those that no weak member reaches on the strong
+    ones', the largest on none: the rows of the penalties differ within every slab, at level 0
+    through the carry and at the later levels (five slabs of 14 members)"""
+    size = 70
+    vectors = [bumps(400, 0, [(64, 96, MANY_STRONG[k])]) if k in MANY_STRONG else
+               bumps(400, 0, [(256, 288, 5 + k % 3)]) for k in range(size)]
+    assert size > SLAB and max(MANY_STRONG) >= SLAB > min(MANY_STRONG)
+    assert len(MANY_PENALTIES) == 16 == _lib().peakseg_hip_joint_path_max_penalties()
+    assert -(-size // LATER_SLAB[16]) == 5
+    models = run_path(psd, wrap, vectors, [0] * size, [0] * size, [[(0, 400)]], MANY_PENALTIES,
+                      "moving peak, many members")
+    ends = {}
+    for penalty, model in zip(MANY_PENALTIES, models):
+        row = model[0]["joint"].iloc[0]
+        ends[penalty] = (int(row["peakStart"]), int(row["peakEnd"]), int(row["samples_up"]))
+    assert len({e[:2] for e in ends.values() if e[0] >= 0}) >= 2      # two penalties, two peaks
+    assert any(e[0] < 0 for e in ends.values())                        # and one without
+    weak = size - len(MANY_STRONG)
+    assert ends[0.0] == ends[1.5] == ends[20.0] == (256, 288, weak)
+    assert ends[60.0][:2] == ends[80.0][:2] == (256, 288) and weak > ends[60.0][2] > ends[80.0][2] > 0
+    assert ends[100.0] == ends[110.0] == ends[150.0] == ends[175.0] == (64, 96, 3)
+    assert ends[200.0] == (64, 96, 2) and ends[240.0] == (64, 96, 1)
+    assert ends[300.0] == ends[1e4] == ends[INF] == (-1, -1, 0)
+    up = models[MANY_PENALTIES.index(200.0)][0]["up"][0]
+    assert np.flatnonzero(up).tolist() == [35, 69]
+
+
+def scenario_many_windows(psd, wrap):
+    """the 300 windows in two groups of tests/test_gpu_joint_peaks.py at 3 penalties: setup_kernel
+    has a thread per (penalty, window), 900 rows in four workgroups, the groups' boundary inside a
+    workgroup of every penalty; then 16 penalties on the first 20 windows, 320 rows"""
+    from test_gpu_joint_peaks import many_windows_case
+    vectors, firsts, groups, windows, peaks = many_windows_case()
+    threads, n = 256, len(windows[0]) + len(windows[1])
+    penalties = [20.0, 1e9, 0.0]
+    assert n == 300 and len(penalties) * n > 3 * threads
+    for p in range(len(penalties)):       # the first row of the second group is no workgroup's first
+        assert (p * n + len(windows[0])) % threads != 0
+    models = run_path(psd, wrap, vectors, firsts, groups, windows, penalties, "many windows")
+    for p in (0, 2):
+        found = [(int(a), int(b)) for entry in models[p]
+                 for a, b in zip(entry["joint"]["peakStart"], entry["joint"]["peakEnd"])]
+        assert found == peaks
+    assert not any((entry["joint"]["peakStart"] >= 0).any() for entry in models[1])
+    every = windows[0] + windows[1]
+    few = [every[:13], every[13:20]]
+    assert threads < len(LADDER) * 20 < 2 * threads
+    models = run_path(psd, wrap, vectors, firsts, groups, few, LADDER, "many windows, 16 penalties")
+    for penalty, model in zip(LADDER, models):
+        found = [(int(a), int(b)) for entry in model
+                 for a, b in zip(entry["joint"]["peakStart"], entry["joint"]["peakEnd"])]
+        assert found == (peaks[:20] if penalty < 1e9 else [(-1, -1)] * 20), penalty
+
+
 # ---- the label-error scenarios -----------------------------------------------------------------
 
 def label_entry(rows):
@@ -395,6 +539,73 @@ def scenario_label_strides(psd, wrap):
     assert model[0, 1] > 0 and model[1, 1] == 0 and model[1, 2] == model[1, 4]
 
 
+def scenario_label_many_problems(psd, wrap):
+    """the 260 problems of scenario_members after a path of the maximum number of penalties:
+    sum_kernel's threads take a second problem each past 256; one to three labels on a problem,
+    none on a few; the problems past 256 have labels that count"""
+    vectors, groups = members_set()
+    n_problems, threads = len(vectors), 256
+    kinds = [[(1060, 1080, PEAK_START)],
+             [(1000, 1200, NO_PEAKS), (1100, 1120, PEAK_END)],
+             [(1050, 1120, PEAKS), (1120, 1190, NO_PEAKS), (1075, 1100, PEAK_START)]]
+    labels = [None if q % 37 == 5 else label_entry(kinds[q % 3]) for q in range(n_problems)]
+    assert threads < n_problems < 2 * threads
+    assert all(labels[q] is not None for q in range(threads, n_problems))
+    assert sum(e is None for e in labels) >= 3
+    assert {len(e[0]) for e in labels if e is not None} == {1, 2, 3}
+    assert len(LADDER) == _lib().peakseg_hip_joint_path_max_penalties()
+    pset = psd.ProblemSet.from_dense([wrap(v) for v in vectors], [(c, INF) for c in range(n_problems)])
+    try:
+        windows = wrap_windows([[(1020, 1180)]] * len(MEMBER_SIZES), wrap)
+        models = pset.joint_path(groups, LADDER, windows=windows, first_chromStart=[1000] * n_problems)
+        model, problem, _ = check_labels(pset, models, labels, wrap)
+    finally:
+        pset.close()
+    for p, penalty in enumerate(LADDER):
+        for g in range(len(MEMBER_SIZES)):
+            assert models[p][g]["joint"]["peakStart"].tolist() == [1070 if penalty < 1e9 else -1]
+    # every total of the problems past 256 differs between a model with peaks and the one without
+    full, empty = LADDER.index(25.0), LADDER.index(1e9)
+    assert problem[full, threads:, 0].tolist() != problem[empty, threads:, 0].tolist()
+    assert problem[:, threads:, 3:].all() and problem[empty, threads:, 0].all()
+    assert model[empty, 0] > model[full, 0] > 0 and len({tuple(row) for row in model.tolist()}) >= 3
+
+
+def scenario_label_full_waves(psd, wrap):
+    """count_kernel packs a wave's four sums into the bytes of one word: 192 `peakStart` labels on
+    one problem, three whole waves of every penalty, around the start of two windows' coinciding
+    peaks: all false positives at penalty 0, all false negatives where there is no peak, so the
+    bytes of both kinds and of both possible kinds hold 64; the same labels shuffled on a second
+    problem"""
+    spans = [(150, 170, 50), (420, 470, 60)]
+    vectors = [bumps(600, 0, spans), bumps(600, 0, [(a, b, h - 9) for a, b, h in spans], base=3)]
+    windows = [[(100, 229), (120, 200)]]
+    ordered = [(150 - j % 48, 151 + j // 48 + j % 5, PEAK_START) for j in range(192)]
+    order = np.random.default_rng(15).permutation(len(ordered))
+    labels = [label_entry(ordered), label_entry([ordered[j] for j in order])]
+    penalties = [0.0, 1e9]
+    wave, n_labels = 64, sum(len(e[0]) for e in labels)
+    assert len(set(ordered)) == len(ordered) == 3 * wave and order.tolist() != sorted(order.tolist())
+    for p in range(len(penalties)):                 # the rows are penalty-major: p * n_labels + row
+        assert (p * n_labels) % wave == 0 and (p * n_labels + len(ordered)) % wave == 0
+    pset = psd.ProblemSet.from_dense([wrap(v) for v in vectors], [(c, INF) for c in range(2)])
+    try:
+        models = pset.joint_path([0, 0], penalties, windows=wrap_windows(windows, wrap))
+        model, problem, rows = check_labels(pset, models, labels, wrap)
+    finally:
+        pset.close()
+    assert models[0][0]["joint"]["peakStart"].tolist() == [150, 150] and models[0][0]["up"].all()
+    assert models[1][0]["joint"]["peakStart"].tolist() == [-1, -1]
+    for q in range(2):                               # (what the yardstick gave, checked above)
+        count, fp, fn = rows[0][q]
+        assert count.tolist() == [2] * 192 and fp.all() and not fn.any()
+        count, fp, fn = rows[1][q]
+        assert not count.any() and not fp.any() and fn.all()
+    assert problem[0].tolist() == [[192, 192, 0, 192, 192]] * 2
+    assert problem[1].tolist() == [[192, 0, 192, 192, 192]] * 2
+    assert model.tolist() == [[384, 384, 0, 384, 384], [384, 0, 384, 384, 384]]
+
+
 def scenario_label_refusals(psd, wrap):
     vectors = moving_peak()
     pset = psd.ProblemSet.from_dense([wrap(v) for v in vectors], [(c, INF) for c in range(4)])
@@ -449,9 +660,11 @@ def scenario_learn(psd, wrap):
 
 
 PATH_SCENARIOS = [scenario_moving_peak, scenario_n_penalties, scenario_members, scenario_widths,
-                  scenario_groups, scenario_solved, scenario_independence]
+                  scenario_groups, scenario_solved, scenario_independence,
+                  scenario_penalty_widths_past_slabs, scenario_moving_peak_many_members,
+                  scenario_many_windows]
 LABEL_SCENARIOS = [scenario_label_relations, scenario_label_models, scenario_label_strides,
-                   scenario_label_refusals]
+                   scenario_label_refusals, scenario_label_many_problems, scenario_label_full_waves]
 SCENARIOS = PATH_SCENARIOS + LABEL_SCENARIOS + [scenario_learn]
 
 

@@ -446,9 +446,37 @@ def scenario_api(psd, wrap):
     assert np.array_equal(one.up, out.groups[1]["up"])
 
 
+def many_windows_case():
+    """300 windows of 40 bases (b = 1, one level) side by side on three contigs of 12 040 bases,
+    a bump in each whose end and height move with the window; two members in the first group with
+    259 windows, one in the second with 41 -> (vectors, firsts, groups, windows, peaks)"""
+    first, n = 20, 300
+    spans = [(first + 40 * k + 10, first + 40 * k + 20 + k % 7, 30 + k % 5) for k in range(n)]
+    vectors = [bumps(12040, first, [(a, b, h + 7 * c) for a, b, h in spans], base=2 + c)
+               for c in range(3)]
+    every = [(first + 40 * k, first + 40 * k + 40) for k in range(n)]
+    return vectors, [first] * 3, [0, 0, 1], [every[:259], every[259:]], [s[:2] for s in spans]
+
+
+def scenario_many_windows(psd, wrap):
+    """300 windows in two groups: setup_kernel has a thread per window, so it needs a second
+    workgroup of 256, and the second workgroup holds the last windows of the first group and all
+    of the second's (its search of win_off gives both answers within one workgroup)"""
+    vectors, firsts, groups, windows, peaks = many_windows_case()
+    threads = 256                                    # joint_peaks.h's THREADS
+    assert threads < len(windows[0]) < len(windows[0]) + len(windows[1]) < 2 * threads
+    assert len(windows[0]) % threads != 0 and len(windows[1]) > 0
+    result, _ = run_case(psd, wrap, vectors, firsts, groups, windows, 20.0, "many windows")
+    found = [(int(a), int(b)) for entry in result
+             for a, b in zip(entry["joint"]["peakStart"], entry["joint"]["peakEnd"])]
+    assert found == peaks
+    assert all(entry["joint"]["levels"].tolist() == [1] * len(entry["joint"]) for entry in result)
+    assert result[0]["up"].all() and result[1]["up"].all()
+
+
 SCENARIOS = [scenario_widths, scenario_wide, scenario_peak_ends, scenario_members, scenario_runs,
              scenario_clipping, scenario_big_counts, scenario_groups, scenario_refusals,
-             scenario_solved, scenario_api]
+             scenario_solved, scenario_api, scenario_many_windows]
 
 
 # ---- MI355X ----------------------------------------------------------------------------------
