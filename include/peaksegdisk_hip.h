@@ -65,6 +65,13 @@ extern "C" {
                                       chromStart >= chromEnd, a problem in a group outside
                                       -1 .. n_groups - 1; the contig and the region, or the problem,
                                       are in peakseg_hip_last_error() */
+#define ERROR_HELDOUT_ARGUMENTS 23 /* pairs that cannot be scored: a negative number of pairs, a NULL
+                                      or misaligned array, a problem or contig out of range, a scale
+                                      that is not finite and positive, a contig that has not the
+                                      bases of its problem's contig; the pair is in
+                                      peakseg_hip_last_error().  Fold sets: a number of folds that is
+                                      not 2, 4 or 8, a base whose count exceeds
+                                      peakseg_hip_fold_max_count() */
 
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
@@ -732,6 +739,97 @@ int peakseg_hip_problem_set_packed_joint_label_errors_download(
     long long *model_totals_out);
 /* milliseconds (HIP events) of the calling thread's last pack_joint_label_errors */
 int peakseg_hip_joint_label_errors_last_ms(float *ms);
+
+/* The Poisson loss of a solved model on ANOTHER contig of the same set: what a penalty chosen by
+ * thinning is scored with (the model is fitted on some of the sampling units, the other contig holds
+ * the units that were held out).  The set is one made by create_dense or create_reads and is
+ * solved.  A PAIR is (problem p, contig c, scale a): contig c must have exactly as many bases as
+ * p's own contig, and positions are base offsets from each contig's first base.  Rows
+ * k = 0 .. S - 1 of p's segments table have [start_k, end_k) and mean_k, the doubles that
+ * peakseg_hip_problem_set_pack_segments reports; B_k = end_k - start_k; Y_k is the `sum` that
+ * peakseg_hip_problem_set_pack_region_stats gives for that region on contig c, an exact int64.
+ * With x_k = a * mean_k the term of row k is
+ *     x_k * B_k - Y_k * psd_log(x_k)   if Y_k > 0 and mean_k > 0,
+ *     x_k * B_k                         if Y_k == 0 (no logarithm is taken),
+ *     +Inf                              if mean_k == 0 and Y_k > 0 (counted in zero_mean_rows),
+ * and loss = sum over k of term_k.  Every product and difference is rounded once (the library is
+ * built with -ffp-contract=off); psd_log is the logarithm of include/peakseg_detmath.h.  The order
+ * of the additions is fixed and depends on S only: with T = 256, the sum s_t of t = 0 .. T - 1 takes
+ * the terms of rows t, t + T, t + 2 T, ... in that order, starting from 0; within every group of 64
+ * consecutive t, for d = 32, 16, 8, 4, 2, 1 in turn, s_t += s_(t + d) for the t whose place in the
+ * group is below 64 - d (all of them from the values before the step); then
+ * loss = ((s_0 + s_64) + s_128) + s_192.  No floating-point atomics are used: the same pairs give
+ * the same bytes on every run.  Per pair the call gives loss (double), rows (int32, S), bases
+ * (int64, the sum of B_k), sum (int64, the sum of Y_k) and zero_mean_rows (int32).  A problem whose
+ * solve reported a failure has no rows, as in pack_segments: its loss is 0 and its rows are 0.
+ *
+ * problem / contig (int32) and scale (double): n_pairs entries each, in host memory or
+ * (pairs_on_device != 0) in the set's device memory, where they are read in place; pairs may
+ * repeat and come in any order.  The *_dev outputs (any may be NULL) receive the device addresses
+ * of the five columns, one entry per pair in the order given; they are valid until the next
+ * pack_heldout_loss or destroy.  The call leaves the segment tables and every other packed buffer
+ * as they are.  The number of launches does not depend on the pairs or the rows.
+ * Returns n_pairs; -1 for a set that was not made from dense counts or reads or is not solved, and
+ * for a device failure; -ERROR_HELDOUT_ARGUMENTS for a negative n_pairs, a NULL or misaligned
+ * array, an index out of range, a scale that is not finite and positive, or a contig whose bases
+ * differ: peakseg_hip_last_error() names the pair.  Host arrays are checked on the host before
+ * anything is allocated or launched; device arrays are checked by the first launch, after which
+ * nothing further is launched.  -ERROR_DEVICE_MEMORY when the call's buffers do not fit in free HBM
+ * or PEAKSEG_HIP_MAX_BYTES: asked before anything is allocated (device arrays: the rows' buffers
+ * are asked about once the first launch has counted the rows, before any of them is allocated). */
+long long peakseg_hip_problem_set_pack_heldout_loss(
+    psd_problem_set *set, long long n_pairs, const int *problem, const int *contig,
+    const double *scale, int pairs_on_device, const double **loss_dev, const int **rows_dev,
+    const long long **bases_dev, const long long **sum_dev, const int **zero_mean_rows_dev);
+/* the five columns of the last pack_heldout_loss to host arrays of n_pairs entries (any may be
+ * NULL); 0, or -1 when nothing is packed or a copy fails */
+int peakseg_hip_problem_set_packed_heldout_loss_download(psd_problem_set *set, double *loss_out,
+                                                         int *rows_out, long long *bases_out,
+                                                         long long *sum_out, int *zero_mean_rows_out);
+/* milliseconds (HIP events) of the calling thread's last pack_heldout_loss: its launches */
+int peakseg_hip_heldout_loss_last_ms(float *ms);
+
+/* Fold sets: the sampling units of every input contig split at random into `folds` = K folds on the
+ * device (thinning), and the set of all train and test contigs.  K is 2, 4 or 8 and
+ * bits = log2 K; any other value is ERROR_HELDOUT_ARGUMENTS.  The random words are splitmix64,
+ *     splitmix64(s, i):  z = s + (i + 1) * 0x9E3779B97F4A7C15;
+ *                        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                        z = (z ^ (z >> 27)) * 0x94D049BB133111EB;   z ^ (z >> 31)
+ * in 64-bit arithmetic that wraps (peaksegdisk_amd/synthetic.py has the same function): with
+ * s_i = seed ^ ((i + 1) * 0xD1B54A32D192ED03) for input contig i, h = splitmix64(s_i, index) and
+ * word_j = splitmix64(h, j).
+ *   dense units  index is the base's offset in its contig.  Unit u < n of a base with the count n
+ *                takes field u mod per_word of word_(u div per_word), where per_word = 64 div bits
+ *                fields of `bits` bits are counted from the low end of a word; the field's value is
+ *                the unit's fold.  (K = 2: the base's count in fold 1 is a popcount.)  The K counts
+ *                t_f of a base sum to n.  A count above peakseg_hip_fold_max_count() = 2^20 is
+ *                refused with ERROR_HELDOUT_ARGUMENTS, the contig and the base in the text: a
+ *                choice, which bounds the words a base takes at 2^20 / 21.
+ *   reads        index is the read's place in the caller's arrays.  The read's fold is the top
+ *                `bits` bits of word_0; its optional count goes whole to that fold.
+ * The set's layout is the same for both: input contig i and fold f give contig (i K + f) 2 (train:
+ * every unit that is not in fold f) and (i K + f) 2 + 1 (test: the units in fold f), both with the
+ * input's bases (reads: its extent); problem (i K + f) P + j is the train contig of (i, f) at
+ * penalties[j], j < P = n_penalties; test contigs carry no problem.  From here on the set is one
+ * of create_dense / create_reads.  The other arguments and statuses are those of the parents; host
+ * arrays are checked on the host, where the input's contig is named (device arrays: a read that
+ * cannot be piled up is named by the pile-up with the fold contig it met it in). */
+int peakseg_hip_problem_set_create_dense_folds(int device, int n_contigs,
+                                               const long long *contig_n_bases,
+                                               const int *const *contig_counts, int counts_on_device,
+                                               int n_penalties, const double *penalties,
+                                               unsigned long long arena_pieces, int folds,
+                                               unsigned long long seed, psd_problem_set **out);
+int peakseg_hip_problem_set_create_reads_folds(
+    int device, int n_contigs, const long long *n_reads, const int *const *read_start,
+    const int *const *read_end, const int *const *read_count, int reads_on_device,
+    const int *extent_start, const int *extent_end, int bases_counted, int n_penalties,
+    const double *penalties, unsigned long long arena_pieces, int folds, unsigned long long seed,
+    psd_problem_set **out);
+/* the largest count of a base that create_dense_folds splits: 2^20 */
+int peakseg_hip_fold_max_count(void);
+/* milliseconds (HIP events) of the calling thread's last fold kernel (dense or reads) */
+int peakseg_hip_fold_units_last_ms(float *ms);
 
 /* The fits of a penalty-learning regression (the model that penalty_model= takes): interval
  * regression with the squared hinge of margin 1, an L1 penalty on the weights and an unpenalised

@@ -19,6 +19,7 @@ ERROR_LABEL_ARGUMENTS = 19
 ERROR_FEATURE_ARGUMENTS = 20
 ERROR_FIT_ARGUMENTS = 21
 ERROR_REGION_ARGUMENTS = 22
+ERROR_HELDOUT_ARGUMENTS = 23
 
 
 class PsdResult(ctypes.Structure):
@@ -295,6 +296,25 @@ def declare(lib):
     lib.peakseg_hip_problem_set_packed_joint_label_errors_download.restype = c.c_int
     lib.peakseg_hip_joint_label_errors_last_ms.argtypes = [c.POINTER(c.c_float)]
     lib.peakseg_hip_joint_label_errors_last_ms.restype = c.c_int
+    lib.peakseg_hip_problem_set_pack_heldout_loss.argtypes = [
+        c.c_void_p, c.c_longlong, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int] + \
+        [c.POINTER(c.c_void_p)] * 5
+    lib.peakseg_hip_problem_set_pack_heldout_loss.restype = c.c_longlong
+    lib.peakseg_hip_problem_set_packed_heldout_loss_download.argtypes = [c.c_void_p] * 6
+    lib.peakseg_hip_problem_set_packed_heldout_loss_download.restype = c.c_int
+    lib.peakseg_hip_heldout_loss_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_heldout_loss_last_ms.restype = c.c_int
+    lib.peakseg_hip_problem_set_create_dense_folds.argtypes = [
+        c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.c_int, c.c_int,
+        c.POINTER(c.c_double), c.c_ulonglong, c.c_int, c.c_ulonglong, c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_create_dense_folds.restype = c.c_int
+    lib.peakseg_hip_problem_set_create_reads_folds.argtypes = reads + [
+        c.c_int, c.POINTER(c.c_double), c.c_ulonglong, c.c_int, c.c_ulonglong, c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_problem_set_create_reads_folds.restype = c.c_int
+    lib.peakseg_hip_fold_max_count.argtypes = []
+    lib.peakseg_hip_fold_max_count.restype = c.c_int
+    lib.peakseg_hip_fold_units_last_ms.argtypes = [c.POINTER(c.c_float)]
+    lib.peakseg_hip_fold_units_last_ms.restype = c.c_int
     lib.peakseg_hip_search_place_penalties.argtypes = [
         c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
     lib.peakseg_hip_search_place_penalties.restype = c.c_int
@@ -353,6 +373,10 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_pack_joint_label_errors",
     "peakseg_hip_problem_set_packed_joint_label_errors_download",
     "peakseg_hip_joint_label_errors_last_ms",
+    "peakseg_hip_problem_set_pack_heldout_loss",
+    "peakseg_hip_problem_set_packed_heldout_loss_download", "peakseg_hip_heldout_loss_last_ms",
+    "peakseg_hip_problem_set_create_dense_folds", "peakseg_hip_problem_set_create_reads_folds",
+    "peakseg_hip_fold_max_count", "peakseg_hip_fold_units_last_ms",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -602,6 +602,94 @@ def PeakSegFPOP_reads(reads, penalties=None, chrom="chrUnknown", extents=None, b
                             penalty_model)
 
 
+# ---- the penalty without labels: thinning and the held-out loss (additive)
+
+def _select_penalty(make_set, penalties, rule, single, label, refit):
+    """What select_penalty_dense and select_penalty_reads share: the fold set of make_set(pens),
+    one solve, one heldout_loss over every (sample, fold, penalty), the selections, and with
+    refit(penalties, one per sample) -> the fits on all the data."""
+    from .heldout import RULES, select_from_set
+    if rule not in RULES:
+        raise ValueError('rule is %r, neither "min" nor "1se"' % (rule,))
+    if penalties is None or len(penalties) == 0:
+        raise ValueError("penalties: the penalties to choose among must be given")
+    pens = []
+    for pen_num in penalties:
+        _check_pen_num(pen_num)
+        pens.append(float(paste(pen_num)))
+    try:
+        pset = make_set(pens)
+    except RuntimeError as e:
+        status = getattr(e, "status", _native.ERROR_DEVICE_SOLVER)
+        msg = _native.status_message(status, label, "", "")
+        detail = _native.last_error()
+        raise PeakSegError(status, "%s (%s)" % (msg, detail) if detail else msg)
+    try:
+        try:
+            pset.solve()
+            chosen = select_from_set(pset, rule)
+        except RuntimeError as e:
+            raise PeakSegError(getattr(e, "status", _native.ERROR_DEVICE_SOLVER), str(e))
+    finally:
+        pset.close()
+    if refit is not None:
+        for sel, fits in zip(chosen, refit([[sel.penalty] for sel in chosen])):
+            sel.fit = fits[0]
+    return chosen[0] if single else chosen
+
+
+def select_penalty_dense(count_vecs, penalties, folds=4, seed=1, rule="min", refit=False,
+                         chrom="chrUnknown", device=0):
+    """The penalty of dense coverage without labels, by K-fold thinning (peaksegdisk_amd/heldout.py;
+    DESIGN.md section 18): every base's unit counts are split at random into `folds` (2, 4 or 8)
+    folds on the GPU, every fold's remaining units are solved at every one of `penalties`, and
+    every model is scored by its Poisson loss on the held-out units -- one fold set, one solve, one
+    ProblemSet.heldout_loss.  count_vecs as PeakSegFPOP_dense takes them; penalties: the numbers to
+    choose among (required: no ladder is invented here), for all vectors; rule: "min" or "1se".
+    Returns a HeldoutSelection for a single vector, else a list of them: .table, .summary,
+    .train_penalty, and .penalty = train_penalty K / (K - 1) for all the data.  refit=True: .fit is
+    PeakSegFPOP_dense's result on the vector at .penalty.  Thinning base by base treats the bases
+    as independent, which coverage that shares reads between neighbouring bases is not: with the
+    reads at hand select_penalty_reads is the sound form, this one the approximation."""
+    from .grid import ProblemSet
+    single = isinstance(count_vecs, np.ndarray) or hasattr(count_vecs, "data_ptr") or (
+        len(count_vecs) > 0 and isinstance(count_vecs[0], (int, np.integer)))
+    vecs = [count_vecs] if single else list(count_vecs)
+    if len(vecs) == 0:
+        raise ValueError("count.vecs must hold at least one vector")
+    contigs = [_int32_vector(v) for v in vecs]
+
+    def fits(per_sample):
+        return PeakSegFPOP_dense(contigs, per_sample, chrom=chrom, device=device)
+    return _select_penalty(
+        lambda pens: ProblemSet.from_dense_folds(contigs, pens, folds=folds, seed=seed, device=device),
+        penalties, rule, single, "<dense counts>", fits if refit else None)
+
+
+def select_penalty_reads(reads, penalties, folds=4, seed=1, rule="min", refit=False,
+                         chrom="chrUnknown", extents=None, bases_counted="each", device=0):
+    """select_penalty_dense for aligned reads: the units are the reads, each of which goes whole
+    (with its optional count) to one fold.  reads, extents and bases_counted as PeakSegFPOP_reads
+    takes them.  Thinned Poisson reads are independent Poisson reads, so the held-out loss is an
+    honest estimate.  refit=True: .fit is PeakSegFPOP_reads' result at .penalty."""
+    from .grid import ProblemSet
+    single, contigs = _read_contigs(reads)
+    names = ("chromStart", "chromEnd", "count")
+    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
+               if isinstance(entry, (tuple, list)) else entry for entry in contigs]
+    if single and extents is not None:
+        extents = [extents]
+
+    def fits(per_sample):
+        return PeakSegFPOP_reads(contigs, per_sample, chrom=chrom, extents=extents,
+                                 bases_counted=bases_counted, device=device)
+    return _select_penalty(
+        lambda pens: ProblemSet.from_reads_folds(contigs, pens, folds=folds, seed=seed,
+                                                 extents=extents, bases_counted=bases_counted,
+                                                 device=device),
+        penalties, rule, single, "<aligned reads>", fits if refit else None)
+
+
 # ---- consensus peaks of several samples (additive; DESIGN.md section 15) ---------------------
 
 class ConsensusPeaks:

@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, joint, joint_path, joint_labels, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, joint, joint_path, joint_labels, heldout, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -97,6 +97,10 @@
 /* the joint peaks at many penalties in one call, and the label errors of every such model */
 #include "joint_path.h"
 #include "joint_labels.h"
+/* the Poisson loss of every model on another contig of the set: what thinning scores a penalty by */
+#include "heldout_loss.h"
+/* the sampling units of dense counts or reads split at random into folds */
+#include "fold_units.h"
 /* tests only: every form of the deterministic exp / log, element by element */
 #include "math_forms_probe.h"
 
@@ -142,6 +146,7 @@
 #include "peakseg_joint.h"
 #include "peakseg_joint_path.h"
 #include "peakseg_joint_labels.h"
+#include "peakseg_heldout.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -194,7 +199,8 @@ extern "C" void peakseg_hip_problem_set_destroy(psd_problem_set *s) {
   for (auto &e : s->features.ev)
     if (e) (void)hipEventDestroy(e);
   for (auto *ev : {s->regions.ev, s->clusters.ev, s->clusters.matrix.ev, s->joint.ev, s->joint.fold.ev,
-                   s->joint_path.ev, s->joint_path.fold.ev, s->joint_labels.ev})
+                   s->joint_path.ev, s->joint_path.fold.ev, s->joint_labels.ev, s->heldout.ev,
+                   s->heldout.fold.ev})
     for (int k = 0; k < 2; k++)
       if (ev[k]) (void)hipEventDestroy(ev[k]);
   if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -565,6 +571,12 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
                 "error code %d: regions or groups that cannot be served (a negative number of regions "
                 "or groups, a NULL or misaligned array, a region with chromStart >= chromEnd, or a "
                 "problem in a group outside -1 .. n_groups - 1)", status);
+    PSD_MESSAGE(ERROR_HELDOUT_ARGUMENTS,
+                "error code %d: pairs that cannot be scored (a negative number of pairs, a NULL or "
+                "misaligned array, a problem or contig out of range, a scale that is not finite and "
+                "positive, or a contig that has not the bases of its problem's contig) or folds that "
+                "cannot be made (a number of folds that is not 2, 4 or 8, or a base whose count "
+                "exceeds peakseg_hip_fold_max_count)", status);
     default:
       snprintf(buf, buf_len, "error code %d", status);
       break;

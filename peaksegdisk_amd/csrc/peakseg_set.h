@@ -176,6 +176,30 @@ struct JointLabelTable {
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
+/* What peakseg_hip_problem_set_pack_heldout_loss keeps (peakseg_heldout.h): the problems'
+ * descriptors, the contigs' bases and the head of a call, the pairs of a call with host arrays, the
+ * two levels of the pairs' row counts, the rows as flat regions with their fold, and the packed
+ * columns.  Every array grows to what the largest call so far needed. */
+struct HeldoutTable {
+  psd::heldout::Problem *d_problems = nullptr; /* per problem */
+  long long *d_contig_bases = nullptr;         /* per contig */
+  psd::heldout::Head *d_head = nullptr;
+  int *d_pairs = nullptr;                      /* 2 x pairs: problem, contig (host arrays only) */
+  double *d_scale = nullptr;                   /* per pair (host arrays only) */
+  long long copy_capacity = 0;
+  int *off = nullptr;                          /* per pair */
+  long long *block_sum = nullptr;              /* per workgroup of pairs_kernel, and the total */
+  double *loss = nullptr;                      /* per pair: the packed columns */
+  int *rows = nullptr, *zero = nullptr;
+  long long *bases = nullptr, *sum = nullptr;
+  long long pair_capacity = 0;
+  int *flat_start = nullptr, *flat_end = nullptr, *flat_contig = nullptr; /* per row */
+  long long row_capacity = 0;
+  RegionTable fold;     /* the fold of the rows */
+  long long pairs = -1; /* of the last call (-1: nothing packed) */
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
 struct psd_problem_set {
   /* geometry: the contigs, the problems and where their tables start */
   int device = 0;
@@ -245,6 +269,7 @@ struct psd_problem_set {
   JointTable joint; /* (sets made from dense counts) */
   JointTable joint_path; /* (sets made from dense counts) */
   JointLabelTable joint_labels; /* (sets made from dense counts) */
+  HeldoutTable heldout; /* (sets made from dense counts) */
 
   /* Sets made from dense counts (peakseg_hip_problem_set_create_dense): run_end[] next to count[]
    * and weight[], the sum of each contig's counts, and which contigs are constant.  Their trivial

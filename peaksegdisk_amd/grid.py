@@ -326,6 +326,111 @@ class ProblemSet:
         self.bins_per_solve = None
         return self
 
+    def _fold_layout(self, n_inputs, penalties, folds, who):
+        """the attributes of a fold set (before the library is called): folds, penalties, problems"""
+        pens = [float(p) for p in penalties]
+        if not pens:
+            raise ValueError("%s: no penalty" % who)
+        self.folds = int(folds)
+        self.fold_inputs = n_inputs
+        self.fold_penalties = pens
+        self.problems = [((i * self.folds + f) * 2, p) for i in range(n_inputs)
+                         for f in range(max(self.folds, 0)) for p in pens]
+        return (ctypes.c_double * len(pens))(*pens)
+
+    def fold_contig(self, i, f, test=False):
+        """the set's contig of input contig i and fold f: the train contig (every unit that is not
+        in fold f), or with test the units in fold f"""
+        if not (0 <= i < self.fold_inputs and 0 <= f < self.folds):
+            raise IndexError("fold_contig: input %d, fold %d" % (i, f))
+        return (i * self.folds + f) * 2 + (1 if test else 0)
+
+    def fold_problem(self, i, f, j):
+        """the set's problem of input contig i, fold f and penalties[j]: its train contig's model"""
+        if not (0 <= i < self.fold_inputs and 0 <= f < self.folds
+                and 0 <= j < len(self.fold_penalties)):
+            raise IndexError("fold_problem: input %d, fold %d, penalty %d" % (i, f, j))
+        return (i * self.folds + f) * len(self.fold_penalties) + j
+
+    @classmethod
+    def from_dense_folds(cls, contigs, penalties, folds=4, seed=1, device=0, arena_pieces=0,
+                         lib=None):
+        """The fold set of DENSE coverage (peakseg_hip_problem_set_create_dense_folds;
+        include/peaksegdisk_hip.h has the definition): the unit counts of every base of every input
+        contig (given as from_dense takes them) are split at random into `folds` (2, 4 or 8) on the
+        device, and the set holds, for input contig i and fold f, the train contig
+        fold_contig(i, f) -- every unit that is not in f -- and the test contig
+        fold_contig(i, f, test=True), both with the input's bases.  Problem fold_problem(i, f, j)
+        is the train contig at penalties[j]; test contigs carry no problem.  From here on the set
+        is one of from_dense.  A number of folds that is not 2, 4 or 8 and a base with more than
+        peakseg_hip_fold_max_count() (2^20) units raise RuntimeError with .status 23."""
+        self = cls.__new__(cls)
+        self._lib = lib or _native.lib
+        self._h = ctypes.c_void_p()
+        self.dense = True
+        self.device = device
+        if len(contigs) == 0:
+            raise ValueError("from_dense_folds: no contig")
+        pens = self._fold_layout(len(contigs), penalties, folds, "from_dense_folds")
+        keep, ptrs, sides = [], [], []
+        for k, v in enumerate(contigs):
+            ptr, n, side, ref = _dense_pointer(k, v, device, "from_dense_folds: contig %d")
+            keep.append(ref)
+            ptrs.append(ptr if n else 0)
+            sides.append(side)
+        if len(set(sides)) != 1:
+            k = next(i for i, sd in enumerate(sides) if sd != sides[0])
+            raise ValueError("from_dense_folds: contig %d is in %s memory but contig 0 is in %s "
+                             "memory; one call takes one kind" % (k, sides[k], sides[0]))
+        nc = len(keep)
+        bases = [int(r.shape[0]) for r in keep]
+        self.contig_bases = [b for b in bases for _ in range(2 * max(self.folds, 0))]
+        st = self._lib.peakseg_hip_problem_set_create_dense_folds(
+            device, nc, (ctypes.c_longlong * nc)(*bases), (ctypes.c_void_p * nc)(*ptrs),
+            1 if sides[0] == "device" else 0, len(self.fold_penalties), pens,
+            ctypes.c_ulonglong(arena_pieces), self.folds, ctypes.c_ulonglong(int(seed) % 2 ** 64),
+            ctypes.byref(self._h))
+        del keep  # (the library holds no reference to the caller's buffers after the call)
+        if st != 0:
+            err = RuntimeError("peakseg_hip_problem_set_create_dense_folds: status %d: %s" % (
+                st, self._lib.peakseg_hip_last_error().decode()))
+            err.status = st
+            raise err
+        self.contigs = None
+        self.bins_per_solve = None
+        return self
+
+    @classmethod
+    def from_reads_folds(cls, reads, penalties, folds=4, seed=1, extents=None, bases_counted="each",
+                         device=0, arena_pieces=0, lib=None):
+        """The fold set of ALIGNED READS (peakseg_hip_problem_set_create_reads_folds): every read
+        (given as from_reads takes them) goes whole, with its optional count, to one of `folds`
+        (2, 4 or 8) folds chosen at random from its place in the caller's arrays; the layout is
+        that of from_dense_folds, the contigs those of from_reads: contig_starts and contig_bases
+        are the extents', repeated for every fold's train and test contig."""
+        self = cls.__new__(cls)
+        self._lib = lib or _native.lib
+        self._h = ctypes.c_void_p()
+        self.dense = True
+        self.device = device
+        args, keep, ext = reads_arguments(reads, extents, bases_counted, device, "from_reads_folds")
+        pens = self._fold_layout(len(reads), penalties, folds, "from_reads_folds")
+        repeat = 2 * max(self.folds, 0)
+        self.contig_starts = [lo for lo, _ in ext for _ in range(repeat)]
+        self.contig_bases = [hi - lo for lo, hi in ext for _ in range(repeat)]
+        st = self._lib.peakseg_hip_problem_set_create_reads_folds(
+            device, *args, len(self.fold_penalties), pens, ctypes.c_ulonglong(arena_pieces),
+            self.folds, ctypes.c_ulonglong(int(seed) % 2 ** 64), ctypes.byref(self._h))
+        del keep  # (the library holds no reference to the caller's buffers after the call)
+        if st != 0:
+            err = RuntimeError("peakseg_hip_problem_set_create_reads_folds: status %d: %s" % (
+                st, self._lib.peakseg_hip_last_error().decode()))
+            err.status = st
+            raise err
+        self.contigs = None
+        self.bins_per_solve = None
+        return self
+
     def segment_columns(self, first_chromStart=None, torch_device=None):
         """The reference's segments table of every problem of a solved set made by from_dense
         (peakseg_hip_problem_set_pack_segments): chromStart, chromEnd and mean in the
@@ -879,6 +984,79 @@ class ProblemSet:
         rows = [[tuple(a[p * total + offs[q]:p * total + offs[q + 1]] for a in cols)
                  for q in range(k)] for p in range(n_pen)]
         return model, totals, rows
+
+    def _pair_column(self, v, dtype, name):
+        """(address, length, "host" | "device", what keeps the memory alive) of a column of
+        heldout_loss(): a tensor on the set's cuda device as it is, anything else as a contiguous
+        numpy array of `dtype` (integers must be integers)"""
+        if type(v).__module__.split(".")[0] == "torch" and hasattr(v, "data_ptr"):
+            import torch
+            if v.device.type == "cuda":
+                want = torch.int32 if dtype == np.int32 else torch.float64
+                index = v.device.index if v.device.index is not None else torch.cuda.current_device()
+                if v.dtype != want or v.dim() != 1 or not v.is_contiguous():
+                    raise ValueError("heldout_loss: %s on the device must be a contiguous 1-d %s "
+                                     "tensor" % (name, want))
+                if index != self.device:
+                    raise ValueError("heldout_loss: %s is on cuda:%d, the set on device %d"
+                                     % (name, index, self.device))
+                return v.data_ptr(), v.shape[0], "device", v
+            v = v.numpy()
+        given = np.asarray(v)
+        a = np.ascontiguousarray(given, dtype=dtype).reshape(-1)
+        if given.ndim > 1 or (dtype == np.int32 and given.size and not np.array_equal(a, given)):
+            raise ValueError("heldout_loss: %s must be a 1-d array of %s"
+                             % (name, "32-bit integers" if dtype == np.int32 else "numbers"))
+        return a.ctypes.data, a.shape[0], "host", a
+
+    def heldout_loss(self, pairs, torch_device=None):
+        """The Poisson loss of the set's models on OTHER contigs of the set, on the device from
+        the resident tables and runs of a solved set made by from_dense or from_reads
+        (peakseg_hip_problem_set_pack_heldout_loss; include/peaksegdisk_hip.h has the definition):
+        what scores a model fitted on part of the sampling units by the units that were held out.
+        pairs: (problem, contig, scale) -- three 1-d arrays of equal length (integers, integers,
+        numbers), or three contiguous tensors on the set's cuda device (int32, int32, float64) that
+        are read in place; one call takes one kind of memory.  Pair i scores the model of problem
+        problem[i] on contig contig[i], which must have the bases of the problem's own contig, with
+        the segment means multiplied by scale[i] > 0.  Pairs may repeat and come in any order.
+        Without torch_device: {"loss": float64[], "rows": int32[], "bases": int64[],
+        "sum": int64[], "zero_mean_rows": int32[]}, one entry per pair (loss is +inf where a
+        segment of mean 0 meets held-out counts; zero_mean_rows counts such segments).  With
+        torch_device: the same dict of tensors that alias the library's buffers: nothing is
+        downloaded, and they are valid until the next heldout_loss() or close().  A pair that
+        cannot be scored raises RuntimeError with .status 23, naming the pair."""
+        if len(pairs) != 3:
+            raise ValueError("heldout_loss: pairs is not (problem, contig, scale)")
+        cols = [self._pair_column(v, dt, name) for v, dt, name in zip(
+            pairs, (np.int32, np.int32, np.float64), ("problem", "contig", "scale"))]
+        n = cols[0][1]
+        for (_, m, side, _), name in zip(cols, ("problem", "contig", "scale")):
+            if m != n:
+                raise ValueError("heldout_loss: %d problems and %d entries of %s" % (n, m, name))
+            if side != cols[0][2]:
+                raise ValueError("heldout_loss: %s is in %s memory but problem is in %s memory; "
+                                 "one call takes one kind" % (name, side, cols[0][2]))
+        out = [ctypes.c_void_p() for _ in range(5)]
+        total = self._lib.peakseg_hip_problem_set_pack_heldout_loss(
+            self._h, n, *[q[0] if n else None for q in cols], 1 if cols[0][2] == "device" else 0,
+            *[ctypes.byref(q) for q in out])
+        del cols  # (the library holds no reference to the caller's buffers after the call)
+        if total < 0:
+            self._raise_status("pack_heldout_loss", total)
+        names = ("loss", "rows", "bases", "sum", "zero_mean_rows")
+        dtypes = (np.float64, np.int32, np.int64, np.int64, np.int32)
+        if torch_device is not None:
+            import torch
+            from .parallel import device_array
+            dev = torch.device(torch_device)
+            return {name: device_array(q.value or 0, n, dt, dev)
+                    for name, q, dt in zip(names, out, dtypes)}
+        result = [np.empty(n, dtype=dt) for dt in dtypes]
+        if self._lib.peakseg_hip_problem_set_packed_heldout_loss_download(
+                self._h, *[a.ctypes.data for a in result]) != 0:
+            raise RuntimeError("packed_heldout_loss_download: %s"
+                               % self._lib.peakseg_hip_last_error().decode())
+        return dict(zip(names, result))
 
     def _coverage_stats(self, ranks, torch_device=None):
         """one peakseg_hip_problem_set_pack_coverage_stats: ranks int64 [n_contigs, k], k at most
