@@ -897,6 +897,11 @@ void peakseg_hip_measured_rates(double *lat_rate, double *thr_rate);
  * builds with -DPSD_SPIN_STATS, 0 otherwise) the largest poll count a problem's waves saw. */
 long long peakseg_hip_spin_limit(void);
 int peakseg_hip_problem_set_max_spin(psd_problem_set *set, int problem);
+/* Tests: in builds with -DPSD_LOOP_STATS, for each chain wave (up, then down) the data points of
+ * the problem's last launch that the latency kernel took inside its inner loop of the usual data
+ * point, those its general code took, and the entries into the inner loop: out[6], returns 6.
+ * Every other build counts nothing and returns 0. */
+int peakseg_hip_problem_set_loop_stats(psd_problem_set *set, int problem, int *out);
 
 /* Change one problem's penalty in place (the contig stays resident, the arena is reused by the
  * next solve): what the penalty search does between its dynamic programs.  0 or -1. */

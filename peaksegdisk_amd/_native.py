@@ -156,6 +156,8 @@ def declare(lib):
     lib.peakseg_hip_spin_limit.restype = c.c_longlong
     lib.peakseg_hip_problem_set_max_spin.argtypes = [c.c_void_p, c.c_int]
     lib.peakseg_hip_problem_set_max_spin.restype = c.c_int
+    lib.peakseg_hip_problem_set_loop_stats.argtypes = [c.c_void_p, c.c_int, c.POINTER(c.c_int)]
+    lib.peakseg_hip_problem_set_loop_stats.restype = c.c_int
     lib.peakseg_hip_last_warning.argtypes = []
     lib.peakseg_hip_last_warning.restype = c.c_char_p
     lib.peakseg_hip_problem_set_arena_stats.argtypes = [
@@ -339,6 +341,7 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_park_stats", "peakseg_hip_problem_set_pack_tables",
     "peakseg_hip_problem_set_packed_download", "peakseg_hip_problem_set_cycles",
     "peakseg_hip_measured_rates", "peakseg_hip_spin_limit", "peakseg_hip_problem_set_max_spin",
+    "peakseg_hip_problem_set_loop_stats",
     "peakseg_hip_last_fanout", "peakseg_hip_last_fanout_entries",
     "PeakSegFPOP_parallel_search", "PeakSegFPOP_parallel_search_batch",
     "peakseg_hip_problem_set_create_dense", "peakseg_hip_problem_set_pack_segments",

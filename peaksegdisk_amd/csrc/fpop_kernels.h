@@ -133,6 +133,35 @@ PSD_D void backtrack_wave(const DeviceArgs &a, int p, int N, BtState &bt, unsign
   bt.status = status;
 }
 
+/* The end of a chain's step: its piece count for the other wave (0 with an error), or the error
+ * for both waves, in the slot of the barrier that follows. */
+PSD_D void step_publish(int lane, int id_own_new, int n_new, unsigned slot) {
+  if (lane == 0) g_sm.n[id_own_new] = n_new < 0 ? 0 : n_new;
+  if (n_new < 0) {
+    if (lane == 0) {
+      g_sm.abort_err[slot] = -n_new;
+      g_sm.abort_status[slot] = ((-n_new) & WERR_ARENA)      ? PST_ARENA_FULL
+                                : ((-n_new) & WERR_OVERFLOW) ? PST_LDS_OVERFLOW
+                                                             : PST_REF_THROW;
+    }
+  }
+}
+
+/* -DPSD_LOOP_STATS (a test build): per chain wave, the data points taken inside the inner loop of
+ * the usual data point, those taken by the general code, and the entries into the inner loop */
+enum { LOOP_INSIDE = 0, LOOP_GENERAL = 1, LOOP_ENTRIES = 2 };
+#undef PSD_LOOP_COUNT
+#ifdef PSD_LOOP_STATS
+#define PSD_LOOP_COUNT(which)                                   \
+  do {                                                          \
+    if (lane_id() == 0) g_sm.loop_stats[wave_id() & 1][which]++; \
+  } while (0)
+#else
+#define PSD_LOOP_COUNT(which) \
+  do {                        \
+  } while (0)
+#endif
+
 /* PSD_KERNEL_WAVES_PER_EU (throughput build): keep the kernel's own register use within the
  * budget of that many waves per SIMD, as the out-of-line operations already are */
 #undef PSD_KERNEL_OCC
@@ -147,14 +176,20 @@ PSD_D void backtrack_wave(const DeviceArgs &a, int p, int N, BtState &bt, unsign
  * CKPT = true: the checkpointed store's passes. */
 template <bool CKPT>
 PSD_D void forward_body(const DeviceArgs &a) {
-  const int p = a.prob_order[blockIdx.x];
+  /* What a problem is made of is the same in every lane, but it is read from tables in HBM that
+   * the compiler will not read with scalar loads: say that it is uniform, or the number of data
+   * points arrives in a vector register, the loop's exit test becomes a vector compare and the
+   * data-point counter with everything derived from it (the lane of the data block, fn_index,
+   * every test of t) moves to vector registers and lane masks with it. */
+  const int p = uniform_i(a.prob_order[blockIdx.x]);
   const int chain = uniform_i(wave_id()) & 1; /* uniform per wave: say so (scalar branches) */
   const int lane = lane_id();
-  const int contig = a.prob_contig[p];
-  const int N = a.contig_n[contig];
-  const double penalty = a.prob_penalty[p];
-  const int *count = a.count + a.contig_off[contig];
-  const int *weight = a.weight + a.contig_off[contig];
+  const int contig = uniform_i(a.prob_contig[p]);
+  const int N = uniform_i(a.contig_n[contig]);
+  const double penalty = uniform_d(a.prob_penalty[p]);
+  const long long contig_off = (long long)uniform_u64((unsigned long long)a.contig_off[contig]);
+  const int *count = a.count + contig_off;
+  const int *weight = a.weight + contig_off;
   const LdsList mlist = lds_list(4 + chain);
   LdsScratch lsc;
   lsc.w = chain;
@@ -171,6 +206,9 @@ PSD_D void forward_body(const DeviceArgs &a) {
     g_sm.arrived[0] = g_sm.arrived[1] = 0xffffffffu;
 #ifdef PSD_SPIN_STATS
     g_sm.spin_max[0] = g_sm.spin_max[1] = g_sm.spin_max[2] = g_sm.spin_max[3] = 0;
+#endif
+#ifdef PSD_LOOP_STATS
+    for (int i = 0; i < 3; i++) g_sm.loop_stats[0][i] = g_sm.loop_stats[1][i] = 0;
 #endif
 #ifdef PSD_PROFILE
     for (int i = 0; i < N_PROF; i++)
@@ -199,7 +237,7 @@ PSD_D void forward_body(const DeviceArgs &a) {
    * in this wave's region of the arena. */
   const int K = CKPT ? a.ckpt_interval : 0;
   const unsigned long long fn_stride = K > 0 ? (unsigned long long)K + 1ull : (unsigned long long)N;
-  const unsigned long long fn_up = (unsigned long long)a.prob_fn_off[p];
+  const unsigned long long fn_up = uniform_u64((unsigned long long)a.prob_fn_off[p]);
   const unsigned long long fn_down = fn_up + fn_stride;
   const unsigned long long fn_mine = chain == 1 ? fn_down : fn_up;
   ArenaCursor cur;
@@ -211,14 +249,16 @@ PSD_D void forward_body(const DeviceArgs &a) {
   double cum_weight_i = 0.0, cum_weight_prev_i = -1.0;
   int cnt_reg = 0, wt_reg = 0;
   int b = 0;        /* buffer holding step t-1 */
-  bool in_hbm = false; /* where the lists of step t-1 live */
+  /* (the flags of the loop are integers, not bools: a uniform bool that lives across blocks is
+   * kept as a 64-bit lane mask and tested through vcc, an integer is tested with a scalar compare) */
+  int in_hbm = 0; /* where the lists of step t-1 live */
   int spill_slot = -1; /* this problem's slot of the HBM spill pool, taken on first overflow */
   int t = 0;
   int t_lo = 0, t_hi = N; /* data points of this pass */
   int t_first = 0;        /* where this pass starts: t_lo, or the data point a parked problem resumes at */
   int t_origin = 0;       /* fn_ref index of data point t: t - t_origin */
   int next_ckpt = K > 0 ? K : -1;
-  bool forward = true;    /* the first pass */
+  int forward = 1;        /* the first pass */
   int step_reached = 0;
   int parked = 0;
   BtState bt;
@@ -233,7 +273,7 @@ PSD_D void forward_body(const DeviceArgs &a) {
   r.prev_seg_end = -1;
   unsigned sync_no = 0; /* parity slot of the abort flags: one per barrier */
   if (lane == 0) g_sm.t_begin[chain] = cycle_now(); /* (in LDS: read once, at the end) */
-  bool resumed_abort = false;
+  int resumed_abort = 0;
   if (!CKPT && a.prob_resume != nullptr) {
     /* A problem parked by an earlier launch (the arena had run out): its two functions, the
      * cumulated weight and its counters come back from the park slot and the pass goes on at
@@ -241,15 +281,15 @@ PSD_D void forward_body(const DeviceArgs &a) {
     const int t_resume = uniform_i(a.prob_resume[p]);
     if (t_resume > 0) {
       device_fence();
-      in_hbm = uniform_i(ckpt_count(*a.self, p, 0, 0)) > LDS_CAP ||
-               uniform_i(ckpt_count(*a.self, p, 0, 1)) > LDS_CAP;
+      in_hbm = (uniform_i(ckpt_count(*a.self, p, 0, 0)) > LDS_CAP ||
+                uniform_i(ckpt_count(*a.self, p, 0, 1)) > LDS_CAP) ? 1 : 0;
       if (in_hbm) {
         spill_slot = uniform_i(take_spill_slot(*a.self, chain));
         if (spill_slot < 0) {
           /* (the pool has no slot yet for these long functions: the park slot stays as it is
            * and the problem resumes here again once the host has enlarged the pool) */
           status = PST_SPILL_FULL;
-          resumed_abort = true;
+          resumed_abort = 1;
           parked = 1;
           step_reached = t_resume;
         }
@@ -260,9 +300,10 @@ PSD_D void forward_body(const DeviceArgs &a) {
         if (lane == 0) g_sm.n[2 * chain] = n_ck;
         cum_weight_i = uniform_d(ckpt_cum_weight(*a.self, p, 0));
         cum_weight_prev_i = cum_weight_i;
-        total_intervals = park_total_intervals(*a.self, p, chain);
-        max_intervals = park_int(*a.self, p, 3 + chain);
-        spill_steps = park_int(*a.self, p, 5);
+        /* (results of calls arrive in vector registers: the statistics are scalar sums) */
+        total_intervals = uniform_u64(park_total_intervals(*a.self, p, chain));
+        max_intervals = uniform_i(park_int(*a.self, p, 3 + chain));
+        spill_steps = uniform_i(park_int(*a.self, p, 5));
         {
           const int n_serial = park_int(*a.self, p, 6 + chain);
           if (lane == 0) g_sm.serial[chain] = n_serial;
@@ -274,13 +315,94 @@ PSD_D void forward_body(const DeviceArgs &a) {
   }
   for (;;) { /* passes */
   if (resumed_abort) break;
+  int reload = 1; /* cnt_reg / wt_reg do not hold the 64 data points around t */
   for (t = t_first; t < t_hi; t++) {
+    int synced = 0; /* the inner loop left this data point after its barrier, with a status */
+#ifndef PSD_CALL_LDS_OPS
+    /* The usual data point (latency build, full store) in a loop of its own: t >= 2, lists in
+     * LDS, functions short enough for chain_step_fast, no error.  It holds what such a data point
+     * does and no call of a cold function, so that what the cold paths need lives around it and
+     * not in it.  Anything else leaves it: a function that outgrew the fast sizes and a rare
+     * argument (-WERR_SERIAL) before anything of the data point is written -- the general code
+     * below computes it -- and a status after the barrier (arena full, an overflow seen by the
+     * other wave, a helper that never came), which the general code's dispatch takes over as it
+     * is.  The pass tries the loop again at the next data point. */
+    if (!CKPT && t >= 2 && !in_hbm) {
+      int entry = 1; /* first data point of this entry: the data block is read whatever t is */
+      cur.store = 1;
+      /* (the statistics: sums in vector registers while the loop runs, see PSD_VECTOR_REG;
+       * spill_steps cannot change here) */
+      unsigned long long total_v = total_intervals;
+      int max_v = max_intervals;
+      PSD_VECTOR_REG(total_v);
+      PSD_VECTOR_REG(max_v);
+      for (;;) {
+        PSD_PROF_T0();
+        const int nb = b ^ 1;
+        const int n_own = uniform_i(g_sm.n[2 * chain + b]);
+        const int n_other = uniform_i(g_sm.n[2 * (1 - chain) + b]);
+        if (n_other > FAST_MAX_OTHER || n_own > FAST_MAX_OWN) break;
+        if (entry || (t & 63) == 0) { /* coalesced read of the next 64 data points */
+          int tt = (t & ~63) + lane;
+          cnt_reg = tt < N ? count[tt] : 0;
+          wt_reg = tt < N ? weight[tt] : 0;
+          if (entry) PSD_LOOP_COUNT(LOOP_ENTRIES);
+          entry = 0;
+        }
+        const int coverage = rdlane_i(cnt_reg, t & 63);
+        const double w = (double)rdlane_i(wt_reg, t & 63);
+        const double cum_weight_new = cum_weight_i + w;
+        /* (penalty / W_{t-1} belongs to min-less: only the up chain divides) */
+        double pen_term = 0.0;
+        if (chain == 0) pen_term = penalty / cum_weight_prev_i;
+        /* (the count comes out of LDS and lane operations: say that it is uniform before it
+         * decides a way out of the loop, or every value the loop carries counts as divergent) */
+        const int n_new = uniform_i(chain_step_fast<USE_HELPER>(
+            a, cur, fn_mine + (unsigned long long)(t - t_origin), chain, t,
+            lds_list(2 * (1 - chain) + b), n_other, lds_list(2 * chain + b), n_own,
+            lds_list(2 * chain + nb), mlist, lsc, pen_term, cum_weight_prev_i, w, coverage,
+            cum_weight_new));
+        if (n_new == -WERR_SERIAL) break; /* nothing written: the general step redoes it */
+        synced = 1;
+        { /* report, meet the other wave (as in the general code below) */
+          PSD_PROF_T0();
+          const unsigned slot = sync_no % 3u;
+          step_publish(lane, 2 * chain + nb, n_new, slot);
+          PSD_PROF_ADD(PROF_ARENA);
+          if (!step_sync(chain, sync_no)) {
+            status = PST_REF_THROW;
+            if (lane == 0) g_sm.abort_err[slot] = WERR_HELPER;
+            break;
+          }
+          PSD_PROF_ADD(PROF_BARRIER);
+          status = uniform_i(g_sm.abort_status[slot]);
+          if (lane == 0) g_sm.abort_status[(sync_no + 2u) % 3u] = 0;
+          sync_no++;
+        }
+        if (status != 0) break;
+        synced = 0;
+        PSD_LOOP_COUNT(LOOP_INSIDE);
+        total_v += (unsigned long long)n_new;
+        if (max_v < n_new) max_v = n_new;
+        cum_weight_i = cum_weight_new;
+        cum_weight_prev_i = cum_weight_i;
+        b = nb;
+        t++;
+        if (t >= t_hi) break;
+      }
+      total_intervals = uniform_u64(total_v);
+      max_intervals = uniform_i(max_v);
+      if (!entry) reload = 1; /* the general code keeps no data block across this loop */
+      if (t >= t_hi) break;
+    }
+#endif
     PSD_PROF_T0();
     if (!CKPT) cur.store = 1; /* known to the compiler even after a cold call returned the cursor */
-    if ((t & 63) == 0 || t == t_first) { /* coalesced read of the next 64 data points */
+    if ((t & 63) == 0 || reload) { /* coalesced read of the next 64 data points */
       int tt = (t & ~63) + lane;
       cnt_reg = tt < N ? count[tt] : 0;
       wt_reg = tt < N ? weight[tt] : 0;
+      reload = 0;
     }
     const int coverage = rdlane_i(cnt_reg, t & 63);
     const double w = (double)rdlane_i(wt_reg, t & 63);
@@ -294,11 +416,12 @@ PSD_D void forward_body(const DeviceArgs &a) {
     /* come back from HBM when both functions fit comfortably again */
     if (in_hbm && n_own <= LDS_CAP / 2 && n_other <= LDS_CAP / 2) {
       move_list_hbm(*a.self, spill_slot, id_own_prev, n_own, 0);
-      in_hbm = false;
+      in_hbm = 0;
       block_sync(chain);
     }
     int n_new = 0;
     for (;;) { /* at most two passes: LDS, then HBM after an overflow */
+      if (!synced) {
       if (t == 0) {
         ArenaCursor cur0 = cur; /* only this copy has its address taken */
         n_new = uniform_i(first_point(*a.self, cur0, fn_index, chain, contig, coverage, id_own_new));
@@ -311,12 +434,14 @@ PSD_D void forward_body(const DeviceArgs &a) {
                            penalty / cum_weight_prev_i, cum_weight_prev_i, w, coverage,
                            cum_weight_new);
 #else
+        /* (full store: the usual case has its own loop above and comes here with what that
+         * loop would not take) */
         n_new = -WERR_SERIAL;
-        if (t >= 2 && n_other <= FAST_MAX_OTHER && n_own <= FAST_MAX_OWN) {
-          n_new = chain_step_fast<USE_HELPER>(
+        if (CKPT && t >= 2 && n_other <= FAST_MAX_OTHER && n_own <= FAST_MAX_OWN) {
+          n_new = uniform_i(chain_step_fast<USE_HELPER>(
               a, cur, fn_index, chain, t, lds_list(id_other_prev), n_other,
               lds_list(id_own_prev), n_own, lds_list(id_own_new), mlist, lsc,
-              penalty / cum_weight_prev_i, cum_weight_prev_i, w, coverage, cum_weight_new);
+              penalty / cum_weight_prev_i, cum_weight_prev_i, w, coverage, cum_weight_new));
         }
         if (n_new == -WERR_SERIAL) { /* not the usual case, or it needs the sequential replay */
           ArenaCursor cur_gen = cur; /* only this copy has its address taken */
@@ -346,15 +471,7 @@ PSD_D void forward_body(const DeviceArgs &a) {
       /* ---- end of pass: report, store the backtrack record, meet the other wave ---- */
       PSD_PROF_T0();
       const unsigned slot = sync_no % 3u;
-      if (lane == 0) g_sm.n[id_own_new] = n_new < 0 ? 0 : n_new;
-      if (n_new < 0) {
-        if (lane == 0) {
-          g_sm.abort_err[slot] = -n_new;
-          g_sm.abort_status[slot] = ((-n_new) & WERR_ARENA)      ? PST_ARENA_FULL
-                                    : ((-n_new) & WERR_OVERFLOW) ? PST_LDS_OVERFLOW
-                                                                 : PST_REF_THROW;
-        }
-      }
+      step_publish(lane, id_own_new, n_new, slot);
       PSD_PROF_ADD(PROF_ARENA);
       if (!step_sync(chain, sync_no)) {
         status = PST_REF_THROW;
@@ -366,6 +483,8 @@ PSD_D void forward_body(const DeviceArgs &a) {
       /* three rotating slots: the one cleared here is first written two barriers later */
       if (lane == 0) g_sm.abort_status[(sync_no + 2u) % 3u] = 0;
       sync_no++;
+      }
+      synced = 0;
 #ifdef PSD_PARK_ON_LDS_OVERFLOW
       /* the packed build: a function that outgrows its short lists is for the throughput build
        * (the problem is parked below and resumed there), not for the HBM path */
@@ -381,7 +500,7 @@ PSD_D void forward_body(const DeviceArgs &a) {
           }
         }
         move_list_hbm(*a.self, spill_slot, id_own_prev, n_own, 1);
-        in_hbm = true;
+        in_hbm = 1;
         status = 0;
         block_sync(chain);
         continue;
@@ -420,6 +539,7 @@ PSD_D void forward_body(const DeviceArgs &a) {
       }
       break;
     }
+    PSD_LOOP_COUNT(LOOP_GENERAL);
     if (!CKPT || forward) {
       total_intervals += (unsigned long long)n_new;
       if (max_intervals < n_new) max_intervals = n_new;
@@ -489,7 +609,7 @@ PSD_D void forward_body(const DeviceArgs &a) {
   if (c < 0) break;
   /* next pass: data points c K + 1 .. (c + 1) K (block 0 also redoes data point 0), from the
    * checkpoint after data point c K, records into this wave's region of the arena */
-  forward = false;
+  forward = 0;
   next_ckpt = -1;
   t_origin = c * K;
   t_lo = c == 0 ? 0 : c * K + 1;
@@ -503,7 +623,7 @@ PSD_D void forward_body(const DeviceArgs &a) {
                  (int)a.ckpt_region);
     cur.store = 1;
   }
-  in_hbm = false;
+  in_hbm = 0;
   b = 0;
   if (c == 0) {
     cum_weight_i = 0.0;
@@ -513,8 +633,8 @@ PSD_D void forward_body(const DeviceArgs &a) {
     device_fence();
     /* functions that do not fit LDS: the block starts with the lists in the HBM spill area
      * (the same decision in both waves: both counts are in the checkpoint) */
-    in_hbm = uniform_i(ckpt_count(*a.self, p, c - 1, 0)) > LDS_CAP ||
-             uniform_i(ckpt_count(*a.self, p, c - 1, 1)) > LDS_CAP;
+    in_hbm = (uniform_i(ckpt_count(*a.self, p, c - 1, 0)) > LDS_CAP ||
+              uniform_i(ckpt_count(*a.self, p, c - 1, 1)) > LDS_CAP) ? 1 : 0;
     if (in_hbm && spill_slot < 0) {
       spill_slot = uniform_i(take_spill_slot(*a.self, chain));
       if (spill_slot < 0) {
@@ -555,6 +675,10 @@ PSD_D void forward_body(const DeviceArgs &a) {
     r.max_spin = 0;
 #ifdef PSD_SPIN_STATS
     for (int w = 0; w < 4; w++) r.max_spin = g_sm.spin_max[w] > r.max_spin ? g_sm.spin_max[w] : r.max_spin;
+#endif
+#ifdef PSD_LOOP_STATS
+    /* (the up wave's counts are complete: the waves met after the pass) */
+    for (int i = 0; i < 6; i++) r.loop_stats[i] = g_sm.loop_stats[i / 3][i % 3];
 #endif
     r.cycles = cycle_now() - g_sm.t_begin[chain];
     if (lane == 0) a.result[p] = r;

@@ -76,6 +76,9 @@ struct SharedBlock {
 #ifdef PSD_SPIN_STATS
   int spin_max[4];
 #endif
+#ifdef PSD_LOOP_STATS
+  int loop_stats[2][3]; /* per chain: data points inside the inner loop, general, entries */
+#endif
   long long t_begin[2];             /* cycle counter at the start of each chain wave */
   unsigned long long cur_ptr[2][3]; /* where each chain's current arena run lives (ArenaCursor) */
 };

@@ -54,6 +54,10 @@ struct ProbResult {
   int parked;             /* PST_ARENA_FULL: the state before data point step_reached is in the
                              problem's park slot, the problem can be resumed there */
   int max_spin;           /* -DPSD_SPIN_STATS builds: largest poll count of a wait between waves */
+#ifdef PSD_LOOP_STATS
+  int loop_stats[6];      /* this launch, per chain: data points taken inside the inner loop of the
+                             usual data point, by the general code, entries into the inner loop */
+#endif
   long long cycles;       /* shader cycles the workgroup ran (this launch) */
 };
 

@@ -512,6 +512,19 @@ extern "C" int peakseg_hip_problem_set_max_spin(psd_problem_set *s, int p) {
   return s->results[(size_t)p].max_spin;
 }
 
+/* builds with -DPSD_LOOP_STATS (tests): per chain wave, the data points of the problem's last
+ * launch taken inside the inner loop of the usual data point, those taken by the general code
+ * and the entries into the inner loop, six numbers; returns 6, or 0 in every other build */
+extern "C" int peakseg_hip_problem_set_loop_stats(psd_problem_set *s, int p, int *out) {
+  if (!s || !s->solved || p < 0 || p >= s->n_problems || !out) return -1;
+#ifdef PSD_LOOP_STATS
+  for (int i = 0; i < 6; i++) out[i] = s->results[(size_t)p].loop_stats[i];
+  return 6;
+#else
+  return 0;
+#endif
+}
+
 /* ---- the dynamic programs of a call on the devices, the file-level solver (the reference's
  *      boundary), the directory-level batch with the cache protocol, the penalty searches ------ */
 #include "peakseg_fanout.h"

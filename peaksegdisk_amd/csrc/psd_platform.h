@@ -222,6 +222,18 @@ PSD_D void lds_add_u32(unsigned *p, unsigned v) {
 }
 #endif
 
+/* Keep a wave-uniform value in a vector register from here on: for sums that a long loop only
+ * adds to, where scalar registers are what the loop is short of (a spilled scalar costs a
+ * v_readlane and a v_writelane per round, the vector add costs one instruction).  uniform_i /
+ * uniform_u64 bring the value back. */
+#ifdef PSD_EMU
+#define PSD_VECTOR_REG(x) \
+  do {                    \
+  } while (0)
+#else
+#define PSD_VECTOR_REG(x) asm("" : "+v"(x))
+#endif
+
 template <class T>
 PSD_D T *uniform_p(T *p) {
 #ifdef PSD_EMU
@@ -231,6 +243,16 @@ PSD_D T *uniform_p(T *p) {
   uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
   uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
   return (T *)(((uint64_t)hi << 32) | lo);
+#endif
+}
+
+PSD_D unsigned long long uniform_u64(unsigned long long v) {
+#ifdef PSD_EMU
+  return v;
+#else
+  uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
 #endif
 }
 

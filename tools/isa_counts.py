@@ -17,7 +17,12 @@ PSD_PROF_SUB in the sources): per phase, the static number of branches, of exec-
 in layout order between two stamps (the fall-through path and the blocks the compiler laid out
 inside it; out-of-line cold blocks are listed under the phase whose stamp follows them).
 
+With --loop-paths the two ends of the usual data point (loop top, end of the data point) are
+measured as shortest paths through the kernel's control-flow graph, for this tree and for any
+other source trees named after the flag (a checkout of the parent commit, say).
+
 usage: python tools/isa_counts.py [--phases] [out.txt]   (no GPU needed)
+       python tools/isa_counts.py --loop-paths [other-tree ...]
 """
 import os
 import re
@@ -96,10 +101,149 @@ def phase_table(csrc, work):
     return out
 
 
+TOP_ANCHORS = [r"const int n_own = uniform_i\(g_sm\.n\[2 \* chain \+ b\]\);",  # the inner loop's top
+               r"if \(\(t & 63\) == 0 \|\| t == t_first\)"]                    # (before it existed)
+STATUS_ANCHOR = r"status = uniform_i\(g_sm\.abort_status\[slot\]\);"
+
+
+def loop_paths(root, work):
+    """The two ends of the usual data point in the latency kernel of the source tree `root`, as
+    shortest paths through the kernel's control-flow graph (one step per instruction; a skip
+    over an exec-mask region, s_cbranch_execz, counts as not taken):
+      top:    from the first instruction of the data-point loop (the inner loop of the usual data
+              point where the tree has one) to the first LDS read of the first pass;
+      bottom: from the read of the barrier's status word (right after step_sync) to the loop's
+              first instruction again.
+    The shortest path is the one without the 64-point data load, errors or cold calls, i.e. what
+    63 of 64 usual data points execute.  Per path: instructions, spill stores (v_writelane of a
+    scalar), spill reloads (v_readlane from a spill register), v_accvgpr moves, uniform
+    conditions made into 64-bit masks (s_cselect_b64 -1, 0), branches through vcc / through scc.
+    Also says where the data-point counter lives (the register incremented at the t++)."""
+    import heapq
+    csrc = os.path.join(root, "peaksegdisk_amd", "csrc")
+    asm = os.path.join(work, "loop.s")
+    flags = [f for f in entry.HIP_FLAGS if f not in ("-shared", "-fPIC")]
+    subprocess.run([entry.HIPCC] + flags + ["--cuda-device-only", "-S", "-gline-tables-only",
+                    "-I" + os.path.join(root, "include"), "-I" + csrc,
+                    os.path.join(csrc, "peakseg_hip.cpp"), "-o", asm], check=True,
+                   stderr=subprocess.DEVNULL)
+    text = open(asm).read()
+    files = {int(m.group(1)): os.path.basename(m.group(3) or m.group(2)) for m in
+             re.finditer(r'\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', text)}
+    start = text.index("\n" + KERNEL + ":")
+    body = text[start:text.index(".end_amdhsa_kernel", start)]
+    src = open(os.path.join(csrc, "fpop_kernels.h")).read().splitlines()
+
+    def src_line(patterns):
+        for pat in patterns:
+            hits = [no for no, ln in enumerate(src, 1) if re.search(pat, ln)]
+            if hits:
+                return hits[0]
+        raise SystemExit("anchor not found in fpop_kernels.h: %r" % (patterns,))
+    top_line, status_line = src_line(TOP_ANCHORS), src_line([STATUS_ANCHOR])
+    insts, locs, label_at = [], [], {}
+    loc = None
+    for ln in body.splitlines():
+        t = ln.split(";")[0].strip()
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
+        if m:
+            loc = (files.get(int(m.group(1)), "?"), int(m.group(2)))
+        elif t.endswith(":"):
+            label_at[t[:-1]] = len(insts)
+        elif t and not t.startswith("."):
+            insts.append(t)
+            locs.append(loc)
+    spill_regs = {m.group(1) for i in insts
+                  for m in [re.match(r"v_writelane_b32 (v\d+), s\d+, \d+", i)] if m}
+
+    def succ(k):
+        i = insts[k]
+        m = re.match(r"s_c?branch\w*\s+(\S+)", i)
+        out = []
+        if m and not i.startswith("s_cbranch_execz"):
+            out.append(label_at[m.group(1)])
+        if not i.startswith(("s_branch", "s_endpgm", "s_setpc")) and k + 1 < len(insts):
+            out.append(k + 1)
+        return out
+
+    def shortest(a, goal):
+        dist, prev, heap = {a: 0}, {}, [(0, a)]
+        while heap:
+            d, k = heapq.heappop(heap)
+            if goal(k) and k != a:
+                path = [k]
+                while path[-1] != a:
+                    path.append(prev[path[-1]])
+                return path[::-1][:-1]  # (the instruction at the goal belongs to what follows)
+            if d > dist[k]:
+                continue
+            for n in succ(k):
+                if n not in dist or d + 1 < dist[n]:
+                    dist[n], prev[n] = d + 1, k
+                    heapq.heappush(heap, (d + 1, n))
+        raise SystemExit("no path")
+    first_of = lambda line: min(k for k, l in enumerate(locs) if l == ("fpop_kernels.h", line))
+    header = first_of(top_line)
+    # (the loop's first instruction: back to the start of the block the anchor's line begins)
+    status = min(k for k, l in enumerate(locs) if l == ("fpop_kernels.h", status_line) and k > header)
+    first_pass = lambda k: insts[k].startswith("ds_read") and locs[k] and \
+        locs[k][0] not in ("fpop_kernels.h", "psd_platform.h")
+    # the way back to the header goes through the increment of the data-point counter (the
+    # shortest path as such would leave the loop as if with an error and enter it again): the
+    # add of 1 to a register that is also masked with 63 (the lane of the data block)
+    lane_regs = {m.group(1) or m.group(2) for i in insts for m in
+                 [re.match(r"(?:s_and_b32 \S+ (s\d+), 63$|v_and_b32\w* \S+ 63, (v\d+)$)", i)] if m}
+    incs = [k for k, i in enumerate(insts) for m in
+            [re.match(r"(?:s_add_i32 (s\d+), \1, 1$|v_add_u32\w* (v\d+), 1, \2$)", i)]
+            if m and (m.group(1) or m.group(2)) in lane_regs]
+    best = None
+    for inc in incs:
+        try:
+            way = shortest(status, lambda k: k == inc) + shortest(inc, lambda k: k == header)
+        except SystemExit:
+            continue
+        if best is None or len(way) < len(best[1]):
+            best = (inc, way)
+    paths = (("top: loop header -> first LDS read of the first pass", shortest(header, first_pass)),
+             ("bottom: status word read after step_sync -> t++ -> loop header", best[1]))
+    out = ["the two ends of the usual data point (%s), shortest paths through the kernel's CFG:"
+           % os.path.basename(os.path.abspath(root))]
+    keys = ("instructions", "spill stores", "spill reloads", "v_accvgpr", "v_mov",
+            "conditions as masks", "vcc branches", "scc branches")
+    for name, path in paths:
+        p = [insts[k] for k in path]
+        n = dict.fromkeys(keys, 0)
+        n["instructions"] = len(p)
+        for i in p:
+            n["spill stores"] += bool(re.match(r"v_writelane_b32 v\d+, s\d+, \d+", i))
+            m = re.match(r"v_readlane_b32 s\d+, (v\d+), \d+", i)
+            n["spill reloads"] += bool(m and m.group(1) in spill_regs)
+            n["v_accvgpr"] += i.startswith("v_accvgpr")
+            n["v_mov"] += i.startswith("v_mov")
+            n["conditions as masks"] += bool(re.match(r"s_cselect_b64 \S+ -1, 0", i))
+            n["vcc branches"] += i.startswith("s_cbranch_vcc")
+            n["scc branches"] += i.startswith("s_cbranch_scc")
+        out.append("  " + name)
+        out.append("    " + ", ".join("%s %d" % (k, n[k]) for k in keys))
+    # the data-point counter: the add of 1 on the path from the status word back to the header
+    out.append("  the data-point counter's increment: %s  (%s register)"
+               % (insts[best[0]], "a scalar" if insts[best[0]].startswith("s_") else "a vector"))
+    return out
+
+
 def main():
     phases = "--phases" in sys.argv
     if phases:
         sys.argv.remove("--phases")
+    if "--loop-paths" in sys.argv:
+        # usage: isa_counts.py --loop-paths [other source tree ...] : this tree, then the others
+        k = sys.argv.index("--loop-paths")
+        work = tempfile.mkdtemp(prefix="psd_isa_")
+        lines = []
+        for root in [ROOT] + sys.argv[k + 1:]:
+            lines += loop_paths(root, work)
+        sys.stdout.write("\n".join(lines) + "\n")
+        return
     csrc = os.path.join(ROOT, "peaksegdisk_amd", "csrc")
     work = tempfile.mkdtemp(prefix="psd_isa_")
     asm = os.path.join(work, "dev.s")
