@@ -72,6 +72,11 @@ extern "C" {
                                       peakseg_hip_last_error().  Fold sets: a number of folds that is
                                       not 2, 4 or 8, a base whose count exceeds
                                       peakseg_hip_fold_max_count() */
+#define ERROR_STRAND_ARGUMENTS 24  /* stranded reads that cannot be served: a strand that is neither
+                                      +1 nor -1, a NULL strand array with reads present, max_shift
+                                      below 0 or above peakseg_hip_xcorr_max_shift(), a
+                                      fragment_length below 1, an extent with hi <= lo; the contig and
+                                      the read, or the argument, are in peakseg_hip_last_error() */
 
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
@@ -942,6 +947,67 @@ int peakseg_hip_reads_pileup_probe(int device, int n_contigs, const long long *n
 /* milliseconds (HIP events) of the calling thread's last pile-up: zeroing and scatter_kernel; the
  * three launches of the prefix sum */
 int peakseg_hip_reads_last_pileup_ms(float *scatter_ms, float *scan_ms);
+
+/* Stranded single-end reads: the strand cross-correlation of the reads' 5'
+ * ends in exact integers, and the extension of reads to a fragment length.  Neither call is tied to
+ * a problem set.
+ *   input    per contig the int32 arrays chromStart, chromEnd and the optional count as
+ *            peakseg_hip_problem_set_create_reads takes them, an int8 array strand with +1 or -1 per
+ *            read, and the extent [lo, hi), B = hi - lo
+ *   tags     the 5' base of a plus read is chromStart, of a minus read chromEnd - 1.  p[i] is the sum
+ *            of the counts of the plus reads whose 5' base is lo + i, m[i] the same for minus reads,
+ *            0 <= i < B.  A read whose 5' base lies outside the extent is no tag; its count still
+ *            goes into the contig's sum of counts, which must stay below 2^31 -- then
+ *            sum p x sum m < 2^62 and every sum below fits 64 bits
+ *   table    for s = 0 .. S = max_shift one row of six int64:
+ *              pairs                max(B - s, 0)
+ *              sum_plus, sq_plus    sum of p[i], of p[i]^2 over i < B - s
+ *              sum_minus, sq_minus  sum of m[i], of m[i]^2 over i >= s
+ *              cross                sum of p[i] m[i + s] over i < B - s
+ *            Integer adds commute: the table does not depend on the schedule, and a repeated call
+ *            gives the same bytes.  S is at most peakseg_hip_xcorr_max_shift() = 1023
+ *   correlation  (formed by the caller from the exact integers; peaksegdisk_amd does it in Python
+ *            integers)  num = pairs cross - sum_plus sum_minus, vx = pairs sq_plus - sum_plus^2,
+ *            vy = pairs sq_minus - sum_minus^2, r = num / (sqrt(vx) sqrt(vy)), NaN where vx <= 0 or
+ *            vy <= 0.  The pooled table of several contigs is the column-wise sum of their tables
+ *            (pooled sums may pass 2^63: not in int64)
+ *   estimate among the shifts of [min_shift, max_shift] with a finite r the largest r, among equal r
+ *            the smallest shift, compared exactly: the sign of num first, then num_a^2 vx_b vy_b
+ *            against num_b^2 vx_a vy_a.  fragment_length = shift + 1: a fragment [f, f + d) has its
+ *            plus tag at f and its minus tag at f + d - 1
+ *   extension  to the length d >= 1: a plus read becomes [chromStart, chromStart + d), a minus read
+ *            [chromEnd - d, chromEnd), formed in 64 bits and clamped into int32.  Nothing is clipped
+ *            to an extent: the pile-up does that afterwards, as for any read
+ * strand_xcorr: table_out is host memory, n_contigs x (max_shift + 1) x 6 int64, contig-major.
+ * extend: fragment_length has one entry per contig; out_start / out_end are on the side of the
+ * inputs (host arrays for host reads, device arrays for device reads; they may be the inputs
+ * themselves); after a refusal their contents are undefined.
+ * Checks, in this order: n_contigs <= 0: ERROR_NO_DATA; what the host sees of the reads --
+ * n_reads < 0, a NULL chromStart / chromEnd with n_reads > 0, an int32 device address that is no
+ * multiple of 4 (a strand array may begin at any byte): ERROR_READS_ARGUMENTS, a NULL strand array
+ * with n_reads > 0: ERROR_STRAND_ARGUMENTS; max_shift or fragment_length out of range, hi <= lo:
+ * ERROR_STRAND_ARGUMENTS; lo < 0: ERROR_READS_ARGUMENTS; the device: ERROR_NO_HIP_DEVICE; whether
+ * the call's buffers fit in free HBM and PEAKSEG_HIP_MAX_BYTES, asked before anything is allocated:
+ * ERROR_DEVICE_MEMORY; then what the first launch finds -- the first read of a contig with
+ * chromStart >= chromEnd or a negative count: ERROR_READS_ARGUMENTS, with a strand that is neither
+ * +1 nor -1: ERROR_STRAND_ARGUMENTS, a contig whose counts sum to 2^31 or more:
+ * ERROR_READS_ARGUMENTS -- with the contig and the read in peakseg_hip_last_error(), and nothing
+ * further is launched. */
+int peakseg_hip_reads_strand_xcorr(int device, int n_contigs, const long long *n_reads,
+                                   const int *const *read_start, const int *const *read_end,
+                                   const int *const *read_count,
+                                   const signed char *const *read_strand, int reads_on_device,
+                                   const int *extent_start, const int *extent_end, int max_shift,
+                                   long long *table_out);
+int peakseg_hip_reads_extend(int device, int n_contigs, const long long *n_reads,
+                             const int *const *read_start, const int *const *read_end,
+                             const signed char *const *read_strand, int reads_on_device,
+                             const int *fragment_length, int *const *out_start, int *const *out_end);
+/* the largest max_shift of one call: 1023 (1024 shifts, four per thread of a workgroup of 256) */
+int peakseg_hip_xcorr_max_shift(void);
+/* milliseconds (HIP events) of the calling thread's last strand_xcorr: zeroing and tags_kernel;
+ * xcorr_kernel and edges_kernel */
+int peakseg_hip_reads_last_xcorr_ms(float *tags_ms, float *xcorr_ms);
 
 /* Tests: the cluster kernels alone, on caller-given peaks of the members of ONE group, without any
  * solve.  n_peaks[m]: the peaks of member m; peak_start[m] / peak_end[m]: host int32 arrays, sorted

@@ -20,6 +20,7 @@ ERROR_FEATURE_ARGUMENTS = 20
 ERROR_FIT_ARGUMENTS = 21
 ERROR_REGION_ARGUMENTS = 22
 ERROR_HELDOUT_ARGUMENTS = 23
+ERROR_STRAND_ARGUMENTS = 24
 
 
 class PsdResult(ctypes.Structure):
@@ -317,6 +318,20 @@ def declare(lib):
     lib.peakseg_hip_fold_max_count.restype = c.c_int
     lib.peakseg_hip_fold_units_last_ms.argtypes = [c.POINTER(c.c_float)]
     lib.peakseg_hip_fold_units_last_ms.restype = c.c_int
+    lib.peakseg_hip_reads_strand_xcorr.argtypes = [
+        c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p), c.POINTER(c.c_void_p), c.c_int, c.POINTER(c.c_int),
+        c.POINTER(c.c_int), c.c_int, c.c_void_p]
+    lib.peakseg_hip_reads_strand_xcorr.restype = c.c_int
+    lib.peakseg_hip_reads_extend.argtypes = [
+        c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p), c.c_int, c.POINTER(c.c_int), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p)]
+    lib.peakseg_hip_reads_extend.restype = c.c_int
+    lib.peakseg_hip_xcorr_max_shift.argtypes = []
+    lib.peakseg_hip_xcorr_max_shift.restype = c.c_int
+    lib.peakseg_hip_reads_last_xcorr_ms.argtypes = [c.POINTER(c.c_float), c.POINTER(c.c_float)]
+    lib.peakseg_hip_reads_last_xcorr_ms.restype = c.c_int
     lib.peakseg_hip_search_place_penalties.argtypes = [
         c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
     lib.peakseg_hip_search_place_penalties.restype = c.c_int
@@ -380,6 +395,8 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_problem_set_packed_heldout_loss_download", "peakseg_hip_heldout_loss_last_ms",
     "peakseg_hip_problem_set_create_dense_folds", "peakseg_hip_problem_set_create_reads_folds",
     "peakseg_hip_fold_max_count", "peakseg_hip_fold_units_last_ms",
+    "peakseg_hip_reads_strand_xcorr", "peakseg_hip_reads_extend", "peakseg_hip_xcorr_max_shift",
+    "peakseg_hip_reads_last_xcorr_ms",
 ]
 
 if not os.path.exists(LIB_PATH):

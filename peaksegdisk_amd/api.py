@@ -573,8 +573,92 @@ def _read_contigs(reads):
     return single, [reads] if single else list(reads)
 
 
+def _strand_vector(v):
+    """a strand column as the library takes it: int8 arrays and tensors as they are, other integer
+    arrays converted (a value that is not +1 or -1 is left for the library to name)"""
+    if hasattr(v, "data_ptr"):
+        return v
+    v = np.asarray(v)
+    if not np.issubdtype(v.dtype, np.integer):
+        raise ValueError("strand must be integer")
+    if v.dtype != np.int8:
+        v = np.where((v == 1) | (v == -1), v, 0).astype(np.int8)
+    return np.ascontiguousarray(v)
+
+
+def _stranded_contigs(reads, strands):
+    """(single, the contigs, the strands) of the public functions of stranded reads, converted as
+    PeakSegFPOP_reads converts its reads"""
+    single, contigs = _read_contigs(reads)
+    names = ("chromStart", "chromEnd", "count")
+    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
+               if isinstance(entry, (tuple, list)) else entry for entry in contigs]
+    if strands is not None:
+        strands = [_strand_vector(v) for v in ([strands] if single else list(strands))]
+    return single, contigs, strands
+
+
+def _strand_call(call):
+    try:
+        return call()
+    except RuntimeError as e:
+        if not hasattr(e, "status"):
+            raise
+        msg = _native.status_message(e.status, "<stranded reads>", "", "")
+        detail = _native.last_error()
+        raise PeakSegError(e.status, "%s (%s)" % (msg, detail) if detail else msg)
+
+
+def strand_cross_correlation(reads, strands, max_shift=400, extents=None, device=0):
+    """The strand cross-correlation of single-end reads, from exact integers computed on the GPU
+    (peakseg_hip_reads_strand_xcorr; the definitions are in include/peaksegdisk_hip.h).  reads as
+    PeakSegFPOP_reads takes them (one contig or a list of contigs, numpy arrays or cuda tensors);
+    strands: per contig an int8 array or tensor with +1 or -1 per read.  A read's tag is its 5'
+    base: chromStart of a plus read, chromEnd - 1 of a minus read.  Returns a list over contigs
+    of data frames with one row per shift 0 .. max_shift (at most 1023): shift, pairs, sum_plus,
+    sq_plus, sum_minus, sq_minus, cross (int64) and correlation = Pearson's r of the plus tags
+    against the minus tags `shift` bases downstream, NaN where a variance is not positive."""
+    from . import strand
+    single, contigs, strands = _stranded_contigs(reads, strands)
+    if single and extents is not None:
+        extents = [extents]
+    tables, _ = _strand_call(lambda: strand.xcorr_tables(contigs, strands, max_shift, extents, device))
+    return [strand.curve_frame(t.tolist()) for t in tables]
+
+
+def estimate_fragment_length(reads, strands, max_shift=400, min_shift=0, extents=None, device=0):
+    """The fragment length of single-end reads from the strand cross-correlation pooled over all
+    contigs (the column-wise sum of their tables): among the shifts min_shift .. max_shift with a
+    finite correlation the one with the largest, the smallest such shift among equals, compared
+    exactly in integers; fragment_length = shift + 1.  min_shift is how a caller steps over the
+    phantom peak at the read length: reads that map uniquely only at some bases correlate across
+    the strands at a shift of about one read length, whatever the fragments are, and a min_shift
+    above the read length keeps that peak out of the choice.  Returns a FragmentLength
+    (fragment_length, shift, correlation, curve); ValueError when no shift has a finite
+    correlation."""
+    from . import strand
+    single, contigs, strands = _stranded_contigs(reads, strands)
+    if single and extents is not None:
+        extents = [extents]
+    return _strand_call(lambda: strand.estimate(contigs, strands, max_shift, min_shift, extents, device))
+
+
+def extend_reads(reads, strands, fragment_length, device=0):
+    """Single-end reads extended from their 5' ends to fragment_length >= 1 on the GPU
+    (peakseg_hip_reads_extend): a plus read becomes [chromStart, chromStart + d), a minus read
+    [chromEnd - d, chromEnd), clamped into int32; count passes through.  fragment_length: an
+    integer or one per contig.  Returns the list over contigs of (chromStart, chromEnd[, count])
+    -- the tuple itself for a single contig -- in the kind of memory it was given (numpy in, numpy
+    out; cuda tensors in, cuda tensors out), which every *_reads entry point takes."""
+    from . import strand
+    single, contigs, strands = _stranded_contigs(reads, strands)
+    out = _strand_call(lambda: strand.extend(contigs, strands, fragment_length, device))
+    return out[0] if single else out
+
+
 def PeakSegFPOP_reads(reads, penalties=None, chrom="chrUnknown", extents=None, bases_counted="each",
-                      device=0, stats=False, labels=None, penalty_model=None):
+                      device=0, stats=False, labels=None, penalty_model=None, strands=None,
+                      fragment_length=None, max_shift=400, min_shift=0):
     """PeakSegFPOP_dense with the step in front of it: aligned reads are piled up into coverage,
     run-length encoded and solved on the GPU.  reads: one contig -- (chromStart, chromEnd) or
     (chromStart, chromEnd, count), one entry per read, in any order -- or a list of contigs
@@ -584,19 +668,21 @@ def PeakSegFPOP_reads(reads, penalties=None, chrom="chrUnknown", extents=None, b
     whose bases are the data, default (min chromStart, max chromEnd) of its reads;
     bases_counted: "each" base of a read or only its "end".  Coordinates are genomic: base 0 of a
     contig is its extent's chromStart.  Results, `stats`, `labels` and `penalty_model` as
-    PeakSegFPOP_dense."""
+    PeakSegFPOP_dense.  Single-end reads: strands= and fragment_length= (an integer, one per
+    contig, or "auto" with max_shift and min_shift) as ProblemSet.from_reads takes them."""
     from .grid import ProblemSet
-    single, contigs = _read_contigs(reads)
-    names = ("chromStart", "chromEnd", "count")
-    contigs = [tuple(None if v is None else _int32_vector(v, names[j]) for j, v in enumerate(entry))
-               if isinstance(entry, (tuple, list)) else entry for entry in contigs]
+    single, contigs, strands = _stranded_contigs(reads, strands)
+    if (strands is None) != (fragment_length is None):
+        raise ValueError("PeakSegFPOP_reads: strands and fragment_length go together")
     if single and extents is not None:
         extents = [extents]
     pens = _penalty_source(penalties, penalty_model, len(contigs), "contig")
 
     def make_set(problems):
         pset = ProblemSet.from_reads(contigs, problems, extents=extents,
-                                     bases_counted=bases_counted, device=device)
+                                     bases_counted=bases_counted, device=device, strands=strands,
+                                     fragment_length=fragment_length, max_shift=max_shift,
+                                     min_shift=min_shift)
         return pset, pset.contig_starts
     return _solve_dense_set(make_set, pens, chrom, stats, single, "<aligned reads>", labels,
                             penalty_model)
@@ -1145,17 +1231,24 @@ def targetInterval_reads(reads, labels, width=None, max_rounds=20, extents=None,
 
 
 def coverage_from_reads(chromStart, chromEnd, count=None, chrom="chrUnknown", extent=None,
-                        bases_counted="each", device=0):
+                        bases_counted="each", device=0, strands=None, fragment_length=None,
+                        max_shift=400, min_shift=0):
     """The coverage profile of one contig's aligned reads, piled up and run-length encoded on the
     GPU (peakseg_hip_reads_pileup_probe): the data frame chrom, chromStart, chromEnd, count that
     writeBedGraph and PeakSegFPOP_df take -- integer columns, genomic coordinates, runs of zero
     included, so there are no gaps.  The read arrays as ProblemSet.from_reads takes them;
-    extent: the (chromStart, chromEnd) to cover, default (min chromStart, max chromEnd)."""
+    extent: the (chromStart, chromEnd) to cover, default (min chromStart, max chromEnd).
+    Single-end reads: strands= (one int8 array or tensor) and fragment_length= (an integer, or
+    "auto" with max_shift and min_shift) extend the reads first, as ProblemSet.from_reads does."""
     import ctypes
     from .grid import reads_arguments
+    from .strand import extended_for
     entry = (chromStart, chromEnd) if count is None else (chromStart, chromEnd, count)
-    args, keep, ext = reads_arguments([entry], None if extent is None else [extent],
-                                      bases_counted, device, "coverage_from_reads")
+    contigs, extents = _strand_call(lambda: extended_for(
+        [entry], None if strands is None else [strands], fragment_length,
+        None if extent is None else [extent], device, None, "coverage_from_reads", max_shift,
+        min_shift))
+    args, keep, ext = reads_arguments(contigs, extents, bases_counted, device, "coverage_from_reads")
     lo, hi = ext[0]
     # a read changes the coverage in at most two places
     capacity = max(1, min(hi - lo, 2 * int(args[1][0]) + 1))

@@ -8,7 +8,7 @@
  *
  * One translation unit: this file instantiates the three kernel builds and holds the thin
  * accessors of the C ABI; the rest of the host side is in the peakseg_*.h it includes, one file
- * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, joint, joint_path, joint_labels, heldout, fanout, files, dir, search), each
+ * per concern (text, set, devices, create, solve, pack, dense, reads, labels, features, fit, regions, clusters, joint, joint_path, joint_labels, heldout, strand, fanout, files, dir, search), each
  * headed by what it holds.
  *
  * Compiled with: hipcc -x hip --offload-arch=gfx950 -ffp-contract=off
@@ -101,6 +101,8 @@
 #include "heldout_loss.h"
 /* the sampling units of dense counts or reads split at random into folds */
 #include "fold_units.h"
+/* the strand cross-correlation of single-end reads, and their extension to a fragment length */
+#include "strand_xcorr.h"
 /* tests only: every form of the deterministic exp / log, element by element */
 #include "math_forms_probe.h"
 
@@ -147,6 +149,7 @@
 #include "peakseg_joint_path.h"
 #include "peakseg_joint_labels.h"
 #include "peakseg_heldout.h"
+#include "peakseg_strand.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -590,6 +593,10 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
                 "positive, or a contig that has not the bases of its problem's contig) or folds that "
                 "cannot be made (a number of folds that is not 2, 4 or 8, or a base whose count "
                 "exceeds peakseg_hip_fold_max_count)", status);
+    PSD_MESSAGE(ERROR_STRAND_ARGUMENTS,
+                "error code %d: stranded reads that cannot be served (a strand that is neither +1 nor "
+                "-1, a NULL strand array, a max_shift outside 0 .. peakseg_hip_xcorr_max_shift, a "
+                "fragment_length below 1, or an extent with hi <= lo)", status);
     default:
       snprintf(buf, buf_len, "error code %d", status);
       break;

@@ -8,21 +8,21 @@ import numpy as np
 from . import _native
 
 
-def _dense_pointer(k, v, device, what="from_dense: contig %d"):
+def _dense_pointer(k, v, device, what="from_dense: contig %d", dtype="int32"):
     """(address, length, "host" | "device", the object that keeps the memory alive) of contig k
-    of ProblemSet.from_dense (`what`: how the messages name it; from_reads names the array too);
-    ValueError for what cannot be passed as it is."""
+    of ProblemSet.from_dense (`what`: how the messages name it; from_reads names the array too;
+    `dtype`: int32, or int8 for strands); ValueError for what cannot be passed as it is."""
     what = what % k
     if isinstance(v, np.ndarray):
-        if v.dtype != np.int32:
-            raise ValueError("%s has dtype %s, not int32" % (what, v.dtype))
+        if v.dtype != np.dtype(dtype):
+            raise ValueError("%s has dtype %s, not %s" % (what, v.dtype, dtype))
         if v.ndim != 1 or not v.flags["C_CONTIGUOUS"]:
             raise ValueError("%s is not a contiguous 1-d array" % what)
         return v.ctypes.data, v.shape[0], "host", v
     if type(v).__module__.split(".")[0] == "torch" and hasattr(v, "data_ptr"):
         import torch
-        if v.dtype != torch.int32:
-            raise ValueError("%s has dtype %s, not int32" % (what, v.dtype))
+        if v.dtype != getattr(torch, dtype):
+            raise ValueError("%s has dtype %s, not %s" % (what, v.dtype, dtype))
         if v.dim() != 1 or not v.is_contiguous():
             raise ValueError("%s is not a contiguous 1-d tensor" % what)
         if v.device.type == "cuda":
@@ -34,8 +34,8 @@ def _dense_pointer(k, v, device, what="from_dense: contig %d"):
         if v.device.type != "cpu":
             raise ValueError("%s is on device %s" % (what, v.device))
         return v.data_ptr(), v.shape[0], "host", v
-    raise ValueError("%s is a %s, not an int32 numpy array or torch tensor"
-                     % (what, type(v).__name__))
+    raise ValueError("%s is a %s, not an %s numpy array or torch tensor"
+                     % (what, type(v).__name__, dtype))
 
 
 ANNOTATIONS = ("noPeaks", "peakStart", "peakEnd", "peaks")  # the codes of label_errors
@@ -290,7 +290,8 @@ class ProblemSet:
 
     @classmethod
     def from_reads(cls, reads, problems, extents=None, bases_counted="each", device=0,
-                   arena_pieces=0, lib=None):
+                   arena_pieces=0, lib=None, strands=None, fragment_length=None, max_shift=400,
+                   min_shift=0):
         """The set of ALIGNED READS: `reads` is a list, one entry per contig, of
         (chromStart, chromEnd) or (chromStart, chromEnd, count) -- 1-d contiguous int32 numpy
         arrays or torch tensors, one entry per read, in any order.  The coverage is piled up and
@@ -301,13 +302,21 @@ class ProblemSet:
         the contig's reads.  bases_counted: "each" base of a read, or only its "end" (last base).
         From here on the set is one of from_dense: contig_bases are the extents' lengths and
         contig_starts their starts, so segment_columns(first_chromStart=pset.contig_starts) gives
-        genomic coordinates."""
+        genomic coordinates.
+        Single-end reads: strands (one int8 array or tensor per contig, +1 or -1 per read) and
+        fragment_length (an integer, one per contig, or "auto": the pooled estimate of the strand
+        cross-correlation over the shifts min_shift .. max_shift) extend every read from its 5'
+        end to the fragment length on the device first (strand.py); the two go together.  Default
+        extents stay those of the reads as given, and the extension is clipped to them."""
+        from .strand import extended_for
         self = cls.__new__(cls)
         self._lib = lib or _native.lib
         self._h = ctypes.c_void_p()
         self.dense = True
         self.device = device
         self.problems = [(int(c), float(p)) for c, p in problems]
+        reads, extents = extended_for(reads, strands, fragment_length, extents, device, self._lib,
+                                      "from_reads", max_shift, min_shift)
         args, keep, ext = reads_arguments(reads, extents, bases_counted, device, "from_reads")
         self.contig_starts = [lo for lo, _ in ext]
         self.contig_bases = [hi - lo for lo, hi in ext]

@@ -94,6 +94,31 @@ def poisson_reads(n_bins, seed=1):
     return start.astype(np.int32), end.astype(np.int32), (0, int(ce[-1]))
 
 
+def stranded_reads(seed, bases, n_sites, per_site, d, jitter, read_length, both):
+    """Single-end reads around binding sites on [0, bases): (chromStart, chromEnd) int32 and the
+    strand int8 (+1 / -1).  uK is uniform01(seed, K, n).  Sites:
+    d + jitter + floor(u11 (bases - 2 (d + jitter) - 2)); each has per_site fragments of the lengths
+    d + floor(u12 (2 jitter + 1)) - jitter, which start at site - floor(u13 length).  both: every
+    fragment [fs, fe) gives a plus read [fs, fs + read_length) and a minus read
+    [fe - read_length, fe), all plus reads first; else one of the two, the plus read iff u14 < 0.5."""
+    n = int(n_sites) * int(per_site)
+    site = d + jitter + np.floor(uniform01(seed, 11, n_sites) * (bases - 2 * (d + jitter) - 2)).astype(np.int64)
+    site = np.repeat(site, per_site)
+    length = d + np.floor(uniform01(seed, 12, n) * (2 * jitter + 1)).astype(np.int64) - jitter
+    fs = site - np.floor(uniform01(seed, 13, n) * length).astype(np.int64)
+    fe = fs + length
+    if both:
+        start = np.concatenate([fs, fe - read_length])
+        end = np.concatenate([fs + read_length, fe])
+        strand = np.concatenate([np.ones(n, np.int8), -np.ones(n, np.int8)])
+    else:
+        plus = uniform01(seed, 14, n) < 0.5
+        start = np.where(plus, fs, fe - read_length)
+        end = np.where(plus, fs + read_length, fe)
+        strand = np.where(plus, 1, -1).astype(np.int8)
+    return start.astype(np.int32), end.astype(np.int32), strand
+
+
 def shuffled(seed, *arrays):
     """the arrays in one seeded random order (reads as an unsorted BAM would give them)"""
     order = np.argsort(uniform01(seed, 7, len(arrays[0])), kind="stable")
