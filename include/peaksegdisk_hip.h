@@ -399,12 +399,47 @@ int peakseg_hip_problem_set_arena_stats(psd_problem_set *set, unsigned long long
 int peakseg_hip_problem_set_park_stats(psd_problem_set *set, int *parks,
                                        unsigned long long *overflow_pool_pieces);
 
+/* ---- The packed results of a set over a history of calls ---------------------------------------
+ * Every pack_* function below keeps its result in device tables of the set, which grow to what the
+ * largest call so far needed and are never shrunk; its ..._download copies the result of the LAST
+ * call to host arrays and returns -1 when nothing is packed.  What ends a packed result, for every
+ * pack_* / ..._download pair (tests/test_gpu_resident_tables.py holds each sentence):
+ *   the same function, called again   Always, also when that call is refused for its arguments or
+ *       for memory: after a refusal nothing is packed, and the next good call is a first call.
+ *   peakseg_hip_problem_set_solve     Every result that describes the set's models or was made
+ *       from them: pack_tables, pack_segments, pack_segment_stats, pack_label_errors,
+ *       pack_peak_clusters, pack_joint_peaks, pack_joint_path, pack_joint_label_errors and
+ *       pack_heldout_loss.  From the solve to the next pack call their downloads return -1 and
+ *       their device addresses must not be read: no download serves the models of the solve
+ *       before.  (pack_joint_peaks and pack_joint_path on GIVEN windows read no model; a solve ends
+ *       their results all the same.)  pack_region_stats and pack_coverage_stats read the contigs
+ *       only: a solve leaves their results as they are, bit for bit.
+ *   another pack_* function           Nothing: every function has tables of its own, and a call
+ *       leaves every other function's result and device addresses as they are.  Two exceptions.
+ *       pack_joint_path ends what pack_joint_label_errors packed (the label errors are those of
+ *       the path).  pack_joint_peaks and pack_joint_path WITHOUT windows take the clusters of their
+ *       groups for windows: they pack those clusters exactly as pack_peak_clusters(the same
+ *       first_chromStart and groups) would, IN ITS PLACE -- afterwards
+ *       packed_peak_clusters_download gives the whole cluster table and matrix of the joint call's
+ *       groups, never a mixture with an earlier pack_peak_clusters; when the clusters cannot be
+ *       packed, nothing is.
+ * Refusals and memory.  A call whose arguments the host can check -- counts, groups, ranks,
+ * penalties, and every entry of arrays given in host memory -- is refused before anything is
+ * allocated: peakseg_hip_problem_set_bytes is what it was.  Arrays in device memory are checked by
+ * the call's first launch, which needs the call's first-level tables.  The functions that return
+ * -ERROR_DEVICE_MEMORY ask whether their tables fit (PEAKSEG_HIP_MAX_BYTES, free memory) before
+ * they allocate them; a call that needs no more than its tables already hold is never refused for
+ * memory.  Growth frees a table before it allocates the larger one, so a set allowed exactly what
+ * it held at the end of a history can repeat that history. */
+
 /* Pack the segment tables of a solved set at their exact sizes, IN HBM: problem p's rows
  * (rows_out[p] of them, n_problems entries, host) follow problem p-1's.  Returns the total
  * number of rows, -1 on failure.  *start_dev / *mean_dev receive the device addresses of the
  * packed arrays (valid until the set is solved again or destroyed): what the multi-GPU gather
  * hands to RCCL without a host round trip (peaksegdisk_amd/parallel.py);
- * peakseg_hip_problem_set_packed_download copies them to host arrays of that many rows. */
+ * peakseg_hip_problem_set_packed_download copies them to host arrays of that many rows, and returns
+ * -1 when the set has been solved again since the last pack call.  No other pack_* function
+ * touches them. */
 long long peakseg_hip_problem_set_pack_tables(psd_problem_set *set, long long *rows_out,
                                               const int **start_dev, const double **mean_dev);
 int peakseg_hip_problem_set_packed_download(psd_problem_set *set, int *start_out, double *mean_out);
@@ -415,7 +450,9 @@ int peakseg_hip_problem_set_packed_download(psd_problem_set *set, int *start_out
  * chromStart (row 0: first + the contig's bases) and its mean; its status is its parity (even:
  * background, odd: peak).  first_chromStart: one per CONTIG, NULL = zeros.  Returns the total
  * number of rows, -1 on failure (a set that was not made from dense counts has no run_end[]).
- * The device addresses stay valid until the set is solved again or destroyed. */
+ * The device addresses stay valid until the set is solved again or destroyed, whatever other pack_*
+ * function is called; ..._download copies the columns and returns -1 when the set has been solved
+ * again since the last pack call, or that call failed. */
 long long peakseg_hip_problem_set_pack_segments(psd_problem_set *set, const int *first_chromStart,
                                                 long long *rows_out, const int **chromStart_dev,
                                                 const int **chromEnd_dev, const double **mean_dev);
@@ -435,8 +472,9 @@ int peakseg_hip_problem_set_packed_segments_download(psd_problem_set *set, int *
  * schedule.  A solved set made from dense counts only (-1 and an error text otherwise).  Returns
  * the total number of rows, -1 on failure; rows_out[p] (n_problems entries, host, may be NULL)
  * receives problem p's row count.  The device addresses stay valid until the set is solved again
- * or destroyed; ..._download copies the columns (any may be NULL) to host arrays of that many rows
- * and returns -1 when the set has been solved again since the last pack call. */
+ * or destroyed, whatever other pack_* function is called; ..._download copies the columns (any may
+ * be NULL) to host arrays of that many rows and returns -1 when the set has been solved again since
+ * the last pack call, or that call failed. */
 long long peakseg_hip_problem_set_pack_segment_stats(psd_problem_set *set, const int *first_chromStart,
                                                      long long *rows_out, const long long **sum_dev,
                                                      const int **max_dev, const int **summitStart_dev,
@@ -472,8 +510,9 @@ int peakseg_hip_segment_stats_last_ms(float *ms);
  * counts; -ERROR_LABEL_ARGUMENTS for what that status names (host arrays are checked on the host,
  * device arrays by the first launch, after which nothing further is launched); the text is in
  * peakseg_hip_last_error.  The device addresses stay valid until the set is solved again, this
- * function is called again, or the set is destroyed; ..._download copies the columns and the
- * totals (any may be NULL) to host arrays and returns -1 when there is nothing packed. */
+ * function is called again, or the set is destroyed, whatever other pack_* function is called;
+ * ..._download copies the columns and the totals (any may be NULL) to host arrays and returns -1
+ * when there is nothing packed: after a solve, and after a refused call. */
 long long peakseg_hip_problem_set_pack_label_errors(
     psd_problem_set *set, const int *first_chromStart, const long long *n_labels,
     const int *const *label_start, const int *const *label_end, const int *const *label_annotation,
@@ -507,8 +546,9 @@ int peakseg_hip_label_errors_last_ms(float *ms);
  * -ERROR_FEATURE_ARGUMENTS for n_ranks < 0 or above the maximum and for a rank outside [0, bases)
  * of its contig, which the host checks before anything is launched; the text is in
  * peakseg_hip_last_error.  The device addresses stay valid until this function is called again or
- * the set is destroyed; ..._download copies value and moments (either may be NULL) to host arrays
- * and returns -1 when there is nothing packed. */
+ * the set is destroyed -- across a solve and across every other pack_* function; ..._download
+ * copies value and moments (either may be NULL) to host arrays and returns -1 when there is
+ * nothing packed (no call yet, or the last call refused). */
 long long peakseg_hip_problem_set_pack_coverage_stats(psd_problem_set *set, int n_ranks,
                                                       const long long *ranks, const int **value_dev,
                                                       const unsigned long long **moments_dev);
@@ -545,8 +585,10 @@ int peakseg_hip_coverage_stats_last_passes(int *digit_passes);
  * -ERROR_REGION_ARGUMENTS for what that status names (host arrays are checked on the host, device
  * arrays by the first launch, after which nothing further is launched); the text is in
  * peakseg_hip_last_error.  The device addresses stay valid until this function is called again or
- * the set is destroyed; ..._download copies the columns (any may be NULL) to host arrays and
- * returns -1 when there is nothing packed. */
+ * the set is destroyed -- across a solve and across every other pack_* function (the cluster
+ * matrix, the joint peaks and the held-out loss fold with tables of their own); ..._download
+ * copies the columns (any may be NULL) to host arrays and returns -1 when there is nothing packed
+ * (no call yet, or the last call refused). */
 long long peakseg_hip_problem_set_pack_region_stats(
     psd_problem_set *set, const int *first_chromStart, const long long *n_regions,
     const int *const *region_start, const int *const *region_end, int regions_on_device,
@@ -590,9 +632,12 @@ int peakseg_hip_region_stats_last_ms(float *ms);
  * counts; -ERROR_REGION_ARGUMENTS for n_groups < 0 or a group value outside [-1, n_groups), with
  * the problem named; -ERROR_DEVICE_MEMORY for a matrix that does not fit (PEAKSEG_HIP_MAX_BYTES or
  * the device), said before anything of it is written; the text is in peakseg_hip_last_error.  The
- * device addresses stay valid until the set is solved again, this function is called again, or the
- * set is destroyed; ..._download copies the columns (any may be NULL) to host arrays and returns -1
- * when there is nothing packed. */
+ * device addresses stay valid until the set is solved again, this function is called again,
+ * pack_joint_peaks or pack_joint_path is called WITHOUT windows (they pack the clusters of their
+ * own groups in this function's tables, as this function would), or the set is destroyed;
+ * ..._download copies the columns (any may be NULL) to host arrays and returns -1 when there is
+ * nothing packed: after a solve, after a refused call of this function, and after such a joint call
+ * whose clusters could not be packed. */
 long long peakseg_hip_problem_set_pack_peak_clusters(
     psd_problem_set *set, const int *first_chromStart, int n_groups, const int *group,
     long long *clusters_out, long long *members_out, const int **clusterStart_dev,
@@ -651,10 +696,14 @@ int peakseg_hip_peak_clusters_last_ms(float *ms);
  * bad group (as pack_peak_clusters), a negative n_windows[g], a NULL or misaligned array, or a given
  * window with start >= end, with the group and the window named (host arrays are checked on the
  * host, device arrays by the first launch); -ERROR_DEVICE_MEMORY when the call's tables do not fit
- * (PEAKSEG_HIP_MAX_BYTES or the device), said before anything of them is allocated.  The device
- * addresses stay valid until the set is solved again, this function is called again, or the set is
- * destroyed; ..._download copies the columns (any may be NULL) and returns -1 when nothing is
- * packed. */
+ * (PEAKSEG_HIP_MAX_BYTES or the device), said before anything of them is allocated.
+ * n_windows == NULL replaces what pack_peak_clusters packed: the call packs the clusters of ITS
+ * groups at ITS first_chromStart in pack_peak_clusters' tables -- columns and matrix, as that
+ * function would -- and packed_peak_clusters_download then gives those (or -1, when the cluster
+ * step was refused); with given windows the cluster tables are not touched.  The device
+ * addresses stay valid until the set is solved again (also where the windows were given), this
+ * function is called again, or the set is destroyed; ..._download copies the columns (any may be
+ * NULL) and returns -1 when nothing is packed. */
 long long peakseg_hip_problem_set_pack_joint_peaks(
     psd_problem_set *set, const int *first_chromStart, int n_groups, const int *group, double penalty,
     const long long *n_windows, const int *const *window_start, const int *const *window_end,
@@ -691,10 +740,12 @@ int peakseg_hip_joint_peaks_last_ms(float *ms);
  * pack_joint_peaks: it depends on the widest window's levels only, not on n_penalties
  * (peaksegdisk_amd/csrc/joint_path.h).
  * The call keeps buffers of its own: a later pack_joint_peaks does not touch what it packed, nor
- * does it touch what pack_joint_peaks packed.  The device addresses stay valid until the set is
- * solved again, this function is called again, or the set is destroyed; ..._download copies the
- * columns (any may be NULL; n_penalties times as many entries each) and returns -1 when nothing is
- * packed. */
+ * does it touch what pack_joint_peaks packed.  n_windows == NULL replaces what pack_peak_clusters
+ * packed by the clusters of this call's groups, exactly as pack_joint_peaks does.  The call ends
+ * what pack_joint_label_errors packed, also when it is refused.  The device addresses stay valid
+ * until the set is solved again (also where the windows were given), this function is called
+ * again, or the set is destroyed; ..._download copies the columns (any may be NULL; n_penalties
+ * times as many entries each) and returns -1 when nothing is packed. */
 int peakseg_hip_joint_path_max_penalties(void);
 long long peakseg_hip_problem_set_pack_joint_path(
     psd_problem_set *set, const int *first_chromStart, int n_groups, const int *group,
@@ -731,9 +782,11 @@ int peakseg_hip_joint_path_last_ms(float *ms);
  * Returns the number of labels of one penalty; -ERROR_LABEL_ARGUMENTS as pack_label_errors, with
  * the problem and the label named (host arrays are checked on the host, device arrays by the first
  * launch).  Two launches, however many penalties, problems, labels and windows
- * (peaksegdisk_amd/csrc/joint_labels.h).  The device addresses stay valid until the next
- * pack_joint_path, this function is called again, or the set is destroyed; ..._download copies the
- * columns (any may be NULL) and returns -1 when nothing is packed. */
+ * (peaksegdisk_amd/csrc/joint_labels.h).  The device addresses stay valid until the set is solved
+ * again (the path is gone with it: the function returns -1 until the next pack_joint_path), the
+ * next pack_joint_path, this function is called again, or the set is destroyed; no other pack_*
+ * function touches them.  ..._download copies the columns (any may be NULL) and returns -1 when
+ * nothing is packed. */
 long long peakseg_hip_problem_set_pack_joint_label_errors(
     psd_problem_set *set, const long long *n_labels, const int *const *label_start,
     const int *const *label_end, const int *const *label_annotation, int labels_on_device,
@@ -771,9 +824,11 @@ int peakseg_hip_joint_label_errors_last_ms(float *ms);
  * problem / contig (int32) and scale (double): n_pairs entries each, in host memory or
  * (pairs_on_device != 0) in the set's device memory, where they are read in place; pairs may
  * repeat and come in any order.  The *_dev outputs (any may be NULL) receive the device addresses
- * of the five columns, one entry per pair in the order given; they are valid until the next
- * pack_heldout_loss or destroy.  The call leaves the segment tables and every other packed buffer
- * as they are.  The number of launches does not depend on the pairs or the rows.
+ * of the five columns, one entry per pair in the order given; they are valid until the set is
+ * solved again (the columns score the models of the solve before: nothing in the library reads
+ * them across a solve, and the download refuses), the next pack_heldout_loss, or destroy.  The call
+ * leaves the segment tables and every other packed buffer as they are.  The number of launches does
+ * not depend on the pairs or the rows.
  * Returns n_pairs; -1 for a set that was not made from dense counts or reads or is not solved, and
  * for a device failure; -ERROR_HELDOUT_ARGUMENTS for a negative n_pairs, a NULL or misaligned
  * array, an index out of range, a scale that is not finite and positive, or a contig whose bases
@@ -787,7 +842,8 @@ long long peakseg_hip_problem_set_pack_heldout_loss(
     const double *scale, int pairs_on_device, const double **loss_dev, const int **rows_dev,
     const long long **bases_dev, const long long **sum_dev, const int **zero_mean_rows_dev);
 /* the five columns of the last pack_heldout_loss to host arrays of n_pairs entries (any may be
- * NULL); 0, or -1 when nothing is packed or a copy fails */
+ * NULL); 0, or -1 when nothing is packed -- no call yet, the last call refused, or the set solved
+ * again since -- or a copy fails */
 int peakseg_hip_problem_set_packed_heldout_loss_download(psd_problem_set *set, double *loss_out,
                                                          int *rows_out, long long *bases_out,
                                                          long long *sum_out, int *zero_mean_rows_out);

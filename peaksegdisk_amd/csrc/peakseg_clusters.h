@@ -221,7 +221,10 @@ int clusters_run(psd_problem_set *s, const int *first_chromStart, int n_groups, 
       more += entry_bytes(entries > 0 ? entries : 1) - entry_bytes(t.entry_capacity);
     size_t free_b = 0, total_b = 0;
     const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-    if ((s->max_bytes && s->bytes + more > s->max_bytes) || (known && more > (unsigned long long)free_b)) {
+    /* (a matrix that needs nothing more fits: the set may hold more than it is allowed by then,
+     * through arrays that are not asked about, and still answers the calls it has room for) */
+    if ((s->max_bytes && more > 0 && s->bytes + more > s->max_bytes) ||
+        (known && more > (unsigned long long)free_b)) {
       set_error("pack_peak_clusters: the matrix of %lld entries needs %llu more bytes, which do not "
                 "fit (free HBM / PEAKSEG_HIP_MAX_BYTES)", entries, more);
       return ERROR_DEVICE_MEMORY;

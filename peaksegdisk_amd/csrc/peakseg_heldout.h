@@ -32,7 +32,9 @@ unsigned long long heldout_row_bytes(long long r) { return (unsigned long long)r
 int heldout_fits(const psd_problem_set *s, unsigned long long more, long long pairs, long long rows) {
   size_t free_b = 0, total_b = 0;
   const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-  if ((s->max_bytes && s->bytes + more > s->max_bytes) || (known && more > (unsigned long long)free_b)) {
+  /* (a call that needs nothing more fits, whatever other services' arrays have grown to) */
+  if ((s->max_bytes && more > 0 && s->bytes + more > s->max_bytes) ||
+      (known && more > (unsigned long long)free_b)) {
     set_error("pack_heldout_loss: %lld pairs of %lld rows need %llu more bytes, which do not fit "
               "(free HBM / PEAKSEG_HIP_MAX_BYTES)", pairs, rows, more);
     return ERROR_DEVICE_MEMORY;

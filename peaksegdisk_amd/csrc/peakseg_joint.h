@@ -179,13 +179,24 @@ int joint_run(psd_problem_set *s, JointTable &t, const char *who, const int *fir
     set_error("%s: %lld windows and %lld entries of the matrix in one call", who, windows, entries);
     return ERROR_REGION_ARGUMENTS;
   }
+  /* given windows in host arrays are checked here, before anything is allocated (setup_kernel
+   * checks what the host cannot see) */
+  for (size_t g = 0; g < ng && n_windows && !on_device; g++)
+    for (long long i = 0; i < counts[g]; i++)
+      if (window_start[g][i] >= window_end[g][i]) {
+        set_error("%s: group %d: window %lld has start %d >= end %d", who, (int)g, i,
+                  window_start[g][i], window_end[g][i]);
+        return ERROR_REGION_ARGUMENTS;
+      }
   /* does it fit?  asked before anything of it is allocated or written */
   {
     const unsigned long long more = joint_room_bytes(s, t, n_groups, members, windows * reps,
                                                      entries * reps, entries * most_slots, carry);
     size_t free_b = 0, total_b = 0;
     const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-    if ((s->max_bytes && s->bytes + more > s->max_bytes) || (known && more > (unsigned long long)free_b)) {
+    /* (a call that needs nothing more fits, whatever other services' arrays have grown to) */
+    if ((s->max_bytes && more > 0 && s->bytes + more > s->max_bytes) ||
+        (known && more > (unsigned long long)free_b)) {
       set_error("%s: the tables of %lld windows and %lld entries need %llu more bytes, "
                 "which do not fit (free HBM / PEAKSEG_HIP_MAX_BYTES)", who, windows * reps,
                 entries * reps, more);
@@ -195,8 +206,7 @@ int joint_run(psd_problem_set *s, JointTable &t, const char *who, const int *fir
   if ((st = joint_room(s, t, n_groups, members, windows * reps, entries * reps, entries * most_slots,
                        carry)))
     return st;
-  /* given windows: where the caller has them, or the library's copy of host arrays (checked here;
-   * setup_kernel checks what the host cannot see) */
+  /* given windows: where the caller has them, or the library's copy of host arrays */
   if (n_windows) {
     std::vector<int> host_copy;
     if (!on_device) host_copy.resize((size_t)(2 * windows));
@@ -208,12 +218,6 @@ int joint_run(psd_problem_set *s, JointTable &t, const char *who, const int *fir
         g_end[g] = window_end[g];
         continue;
       }
-      for (long long i = 0; i < m; i++)
-        if (window_start[g][i] >= window_end[g][i]) {
-          set_error("%s: group %d: window %lld has start %d >= end %d", who, (int)g, i,
-                    window_start[g][i], window_end[g][i]);
-          return ERROR_REGION_ARGUMENTS;
-        }
       memcpy(host_copy.data() + at, window_start[g], sizeof(int) * (size_t)m);
       memcpy(host_copy.data() + windows + at, window_end[g], sizeof(int) * (size_t)m);
       g_start[g] = t.d_windows + at;

@@ -39,6 +39,16 @@ int joint_labels_run(psd_problem_set *s, const long long *n_labels, const int *c
     set_error("pack_joint_label_errors: %lld rows and %lld totals in one call", rows, cells);
     return ERROR_LABEL_ARGUMENTS;
   }
+  /* host arrays are checked here, before anything is allocated (count_kernel checks what the host
+   * cannot see) */
+  for (size_t q = 0; q < np && !on_device; q++)
+    for (long long i = 0; i < n_labels[q]; i++) {
+      const int ls = label_start[q][i], le = label_end[q][i], a = label_annotation[q][i];
+      if (ls >= le || a < 0 || a > 3) {
+        joint_label_error_text((int)q, i, ls, le, a, true);
+        return ERROR_LABEL_ARGUMENTS;
+      }
+    }
   for (auto &e : t.ev)
     if (!e) HIP_TRY(hipEventCreate(&e));
   /* (the set's geometry: their sizes never change) */
@@ -67,8 +77,7 @@ int joint_labels_run(psd_problem_set *s, const long long *n_labels, const int *c
     if ((st = label_room(s, t.totals, jl::TOTALS * have, jl::TOTALS * need))) return st;
     t.total_capacity = need;
   }
-  /* the problems' labels: where the caller has them, or the library's copy of host arrays (checked
-   * here: count_kernel checks what the host cannot see) */
+  /* the problems' labels: where the caller has them, or the library's copy of host arrays */
   std::vector<jl::Problem> problems(np);
   std::vector<int> host_copy;
   if (!on_device) host_copy.resize((size_t)(3 * n_all));
@@ -78,13 +87,6 @@ int joint_labels_run(psd_problem_set *s, const long long *n_labels, const int *c
     const int *from[3] = {n ? label_start[q] : nullptr, n ? label_end[q] : nullptr,
                           n ? label_annotation[q] : nullptr};
     if (!on_device) {
-      for (long long i = 0; i < n; i++) {
-        const int ls = from[0][i], le = from[1][i], a = from[2][i];
-        if (ls >= le || a < 0 || a > 3) {
-          joint_label_error_text((int)q, i, ls, le, a, true);
-          return ERROR_LABEL_ARGUMENTS;
-        }
-      }
       for (int j = 0; j < 3; j++) {
         if (n) memcpy(host_copy.data() + j * n_all + off, from[j], sizeof(int) * (size_t)n);
         from[j] = t.d_labels + j * n_all + off;

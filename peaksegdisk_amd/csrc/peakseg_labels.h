@@ -57,6 +57,16 @@ int labels_run(psd_problem_set *s, const int *first_chromStart, const long long 
     set_error("pack_label_errors: %lld rows in one call", total);
     return ERROR_LABEL_ARGUMENTS;
   }
+  /* host arrays are checked here, before anything is allocated (translate_kernel checks what the
+   * host cannot see) */
+  for (size_t c = 0; c < nc && !on_device; c++)
+    for (long long i = 0; i < n_labels[c]; i++) {
+      const int ls = label_start[c][i], le = label_end[c][i], a = label_annotation[c][i];
+      if (ls >= le || a < 0 || a > 3) {
+        label_error_text((int)c, i, ls, le, a, true);
+        return ERROR_LABEL_ARGUMENTS;
+      }
+    }
   for (auto &e : t.ev)
     if (!e) HIP_TRY(hipEventCreate(&e));
   /* (the set's geometry: their sizes never change) */
@@ -84,8 +94,7 @@ int labels_run(psd_problem_set *s, const int *first_chromStart, const long long 
       return st;
     t.row_capacity = need;
   }
-  /* the contigs' labels: where the caller has them, or the library's copy of host arrays (checked
-   * here: translate_kernel checks what the host cannot see) */
+  /* the contigs' labels: where the caller has them, or the library's copy of host arrays */
   std::vector<lb::Contig> contigs(nc);
   std::vector<int> host_copy;
   if (!on_device) host_copy.resize((size_t)(3 * n_all));
@@ -95,13 +104,6 @@ int labels_run(psd_problem_set *s, const int *first_chromStart, const long long 
     const int *from[3] = {n ? label_start[c] : nullptr, n ? label_end[c] : nullptr,
                           n ? label_annotation[c] : nullptr};
     if (!on_device) {
-      for (long long i = 0; i < n; i++) {
-        const int ls = from[0][i], le = from[1][i], a = from[2][i];
-        if (ls >= le || a < 0 || a > 3) {
-          label_error_text((int)c, i, ls, le, a, true);
-          return ERROR_LABEL_ARGUMENTS;
-        }
-      }
       for (int j = 0; j < 3; j++) {
         if (n) memcpy(host_copy.data() + j * n_all + off, from[j], sizeof(int) * (size_t)n);
         from[j] = t.d_labels + j * n_all + off;

@@ -76,6 +76,7 @@ extern "C" long long peakseg_hip_problem_set_pack_tables(psd_problem_set *s, lon
                                                          const double **mean_dev) {
   if (!s || !s->solved) return -1;
   if (hipSetDevice(s->device) != hipSuccess) return -1;
+  s->run.pack_total = -1; /* (nothing is packed after a call that fails) */
   std::vector<long long> rows((size_t)3 * (size_t)s->n_problems);
   PackedTable &t = s->pack;
   const long long total = pack(s, t, PACK_COLS, rows, rows_out, "segment tables", [&]() {
@@ -109,6 +110,7 @@ extern "C" long long peakseg_hip_problem_set_pack_segments(psd_problem_set *s,
     return -1;
   }
   if (hipSetDevice(s->device) != hipSuccess) return -1;
+  s->run.segs_total = -1; /* (nothing is packed after a call that fails) */
   std::vector<long long> rows((size_t)6 * (size_t)s->n_problems);
   long long *lay = rows.data() + (size_t)3 * (size_t)s->n_problems;
   for (int p = 0; p < s->n_problems; p++) {
@@ -256,6 +258,7 @@ extern "C" long long peakseg_hip_problem_set_pack_segment_stats(
     return -1;
   }
   if (hipSetDevice(s->device) != hipSuccess) return -1;
+  s->run.stats_total = -1; /* (nothing is packed after a call that fails) */
   for (int c = 0; c < s->n_contigs; c++) {
     const long long first = first_chromStart ? first_chromStart[c] : 0;
     if (first < 0 || first + s->contig_bases[(size_t)c] > 2147483647ll) {
@@ -265,7 +268,6 @@ extern "C" long long peakseg_hip_problem_set_pack_segment_stats(
     }
   }
   long long total = 0;
-  s->run.stats_total = -1;
   if (stats_run(s, first_chromStart, rows_out, &total)) return -1;
   s->run.stats_total = total;
   if (sum_dev) *sum_dev = s->stats.sum;

@@ -148,6 +148,14 @@ int regions_run(psd_problem_set *s, const int *first_chromStart, const long long
     set_error("pack_region_stats: %lld regions in one call", n);
     return ERROR_REGION_ARGUMENTS;
   }
+  /* host arrays are checked here, before anything is allocated (locate_kernel checks what the host
+   * cannot see) */
+  for (size_t c = 0; c < nc && !on_device; c++)
+    for (long long i = 0; i < n_regions[c]; i++)
+      if (region_start[c][i] >= region_end[c][i]) {
+        region_error_text((int)c, i, region_start[c][i], region_end[c][i], true);
+        return ERROR_REGION_ARGUMENTS;
+      }
   if ((st = regions_room(s, t, n))) return st;
   std::vector<const int *> start(nc, nullptr), end(nc, nullptr);
   std::vector<int> host_copy;
@@ -160,11 +168,6 @@ int regions_run(psd_problem_set *s, const int *first_chromStart, const long long
       end[c] = region_end[c];
       continue;
     }
-    for (long long i = 0; i < m; i++)
-      if (region_start[c][i] >= region_end[c][i]) {
-        region_error_text((int)c, i, region_start[c][i], region_end[c][i], true);
-        return ERROR_REGION_ARGUMENTS;
-      }
     memcpy(host_copy.data() + at, region_start[c], sizeof(int) * (size_t)m);
     memcpy(host_copy.data() + n + at, region_end[c], sizeof(int) * (size_t)m);
     start[c] = t.d_regions + at;

@@ -526,6 +526,13 @@ extern "C" int peakseg_hip_problem_set_solve(psd_problem_set *s, float *forward_
     d_order_first = s->d_order_run;
   }
   s->run = SolveRun();
+  /* ... and with it what the other pack_* services packed of the models before: their downloads
+   * say "nothing packed" until they are called again (region and coverage stats read no model) */
+  s->clusters.clusters = s->clusters.entries = -1;
+  s->joint.windows = s->joint.entries = -1;
+  s->joint_path.windows = s->joint_path.entries = -1;
+  s->joint_labels.labels = -1;
+  s->heldout.pairs = -1;
   s->run.plan = plan_solve(len, s->n_cu, s->can_park, PlanKnobs());
   /* Launches.  The first one runs every problem.  When problems come back unfinished for
    * want of room (arena, spill pool, checkpoint overflow pool) the host enlarges what was short

@@ -763,7 +763,8 @@ class ProblemSet:
         PeakSegPipeline's PeakSegJoint step), on the device from the resident runs of a set made by
         from_dense or from_reads.  groups as for peak_clusters().  penalty >= 0: the price of one
         more member with a peak.  windows: None -- the windows are the clusters of peak_clusters()
-        (a solved set), each widened by its own width on either side -- or a list over GROUPS of
+        (a solved set), each widened by its own width on either side; the call then packs those
+        clusters in place of what peak_clusters() packed -- or a list over GROUPS of
         (start, end), 1-d contiguous int32 numpy arrays or torch tensors (an empty entry or None: no
         windows); tensors on the set's cuda device are read in place; one call takes one kind of
         memory; no solve is needed.  Every window is clipped to the extent all members of its group
@@ -926,7 +927,8 @@ class ProblemSet:
         arrays of problem q's labels in model p.  With torch_device the totals and the three
         columns ([n_penalties, labels], problem after problem) are tensors that alias the library's
         buffers, as (offsets int64 numpy[n_problems + 1], count, fp, fn, problem_totals,
-        model_totals), valid until the next joint_path(), joint_label_errors() or close()."""
+        model_totals), valid until the next solve(), joint_path(), joint_label_errors() or
+        close()."""
         k = len(self.problems)
         if len(labels) != k:
             raise ValueError("joint_label_errors: one entry per problem (%d entries, %d problems)"
@@ -1032,7 +1034,7 @@ class ProblemSet:
         "sum": int64[], "zero_mean_rows": int32[]}, one entry per pair (loss is +inf where a
         segment of mean 0 meets held-out counts; zero_mean_rows counts such segments).  With
         torch_device: the same dict of tensors that alias the library's buffers: nothing is
-        downloaded, and they are valid until the next heldout_loss() or close().  A pair that
+        downloaded, and they are valid until the next solve(), heldout_loss() or close().  A pair that
         cannot be scored raises RuntimeError with .status 23, naming the pair."""
         if len(pairs) != 3:
             raise ValueError("heldout_loss: pairs is not (problem, contig, scale)")
