@@ -77,6 +77,10 @@ extern "C" {
                                       below 0 or above peakseg_hip_xcorr_max_shift(), a
                                       fragment_length below 1, an extent with hi <= lo; the contig and
                                       the read, or the argument, are in peakseg_hip_last_error() */
+#define ERROR_DEDUP_ARGUMENTS 25   /* a duplicate removal or compaction that cannot be served: keep
+                                      below 1, an unknown `by`, five_prime without strands, 2^31 or
+                                      more rows in one call, an output that overlaps an input; the
+                                      argument is in peakseg_hip_last_error() */
 
 /* ---- environment ---------------------------------------------------------------------
  * PEAKSEG_HIP_DEVICE            GPU used by the file-level entry points (default 0); one process
@@ -1064,6 +1068,64 @@ int peakseg_hip_xcorr_max_shift(void);
 /* milliseconds (HIP events) of the calling thread's last strand_xcorr: zeroing and tags_kernel;
  * xcorr_kernel and edges_kernel */
 int peakseg_hip_reads_last_xcorr_ms(float *tags_ms, float *xcorr_ms);
+
+/* Duplicate removal of aligned reads: the first `keep` units of every key
+ * survive, in input order, in exact integers.  Neither call is tied to a problem set.
+ *   input    per contig the reads i = 0 .. n - 1 in input order: int32 chromStart[i] < chromEnd[i]
+ *            (negative coordinates are legal, as in the pile-up), an optional int32 count[i] >= 0
+ *            (absent: every read counts 1) and an optional int8 strand[i] of +1 or -1.  c(i) is the
+ *            count of read i: a row is a multiplicity
+ *   key      by = 0 (fragment): (chromStart, chromEnd, strand), the strand +1 for every read when no
+ *            strand array is given -- paired-end fragments, reads used as they are.  by = 1
+ *            (five_prime): (5' base, strand), the 5' base chromStart of a plus read and chromEnd - 1
+ *            of a minus read; a strand array is required -- the rule for single-end reads.  Keys are
+ *            compared within a contig only
+ *   marking  with keep in 1 .. 2^31 - 1:
+ *              before(i)    = sum of c(j) over j < i with key(j) = key(i)
+ *              out_count(i) = min(c(i), max(keep - before(i), 0))
+ *            The result depends on grouping and input order only, never on how keys are ordered
+ *            among themselves
+ *   summary  per contig four int64: reads = sum of c(i), kept = sum of out_count(i), rows_kept =
+ *            #{i: out_count(i) > 0}, distinct = #{i: c(i) > 0 and before(i) = 0}, the keys with at
+ *            least one unit.  Everything is integer; a repeated call gives the same bytes
+ * dedup: out_count[c] (n_reads[c] int32) is on the side of the inputs -- host arrays for host reads,
+ * device arrays for device reads -- and must not overlap any input; summary_out is host memory,
+ * 4 x n_contigs.  read_strand may be NULL for by = 0.
+ * compact: writes the rows with keep_count > 0 of every contig, in order, to out_start / out_end /
+ * out_count (the value of keep_count) and, with read_strand given, out_strand -- room for n_reads[c]
+ * rows each, on the side of the inputs, overlapping no input -- and the rows written per contig to
+ * rows_out (host).  Usable on its own, for instance to drop rows of count 0.
+ * Checks, in this order: n_contigs <= 0: ERROR_NO_DATA; n_reads NULL or negative:
+ * ERROR_READS_ARGUMENTS; 2^31 or more rows in the call, an unknown by, keep < 1, five_prime without
+ * strands: ERROR_DEDUP_ARGUMENTS; a NULL array of a contig with reads or an int32 device address that
+ * is no multiple of 4 (a strand array may begin at any byte): ERROR_READS_ARGUMENTS, a NULL strand
+ * array next to given ones: ERROR_STRAND_ARGUMENTS; an output that overlaps an input:
+ * ERROR_DEDUP_ARGUMENTS; the device: ERROR_NO_HIP_DEVICE; whether the call's buffers fit in free HBM
+ * and PEAKSEG_HIP_MAX_BYTES, asked before anything is allocated: ERROR_DEVICE_MEMORY; then what the
+ * first launch finds -- the first read of a contig with chromStart >= chromEnd or a negative count:
+ * ERROR_READS_ARGUMENTS, with a strand that is neither +1 nor -1: ERROR_STRAND_ARGUMENTS, a contig
+ * whose counts sum to 2^31 or more (the pile-up's rule; what makes before(i) fit int32):
+ * ERROR_READS_ARGUMENTS -- with the contig and the read in peakseg_hip_last_error(), and nothing
+ * further is launched.  A refused call has written nothing to its outputs. */
+int peakseg_hip_reads_dedup(int device, int n_contigs, const long long *n_reads,
+                            const int *const *read_start, const int *const *read_end,
+                            const int *const *read_count, const signed char *const *read_strand,
+                            int reads_on_device, int by, int keep, int *const *out_count,
+                            long long *summary_out);
+int peakseg_hip_reads_compact(int device, int n_contigs, const long long *n_reads,
+                              const int *const *read_start, const int *const *read_end,
+                              const signed char *const *read_strand, int reads_on_device,
+                              const int *const *keep_count, int *const *out_start,
+                              int *const *out_end, int *const *out_count,
+                              signed char *const *out_strand, long long *rows_out);
+/* rows of a workgroup of a sort pass, and the workgroups one trip of the table scan covers: what the
+ * tests build their sizes on */
+int peakseg_hip_dedup_block_rows(void);
+int peakseg_hip_dedup_scan_span(void);
+/* milliseconds (HIP events) of the calling thread's last dedup: zeroing and keys_kernel; the sort's
+ * passes; the three launches of the runs -- and the number of passes the keys' mask chose */
+int peakseg_hip_reads_last_dedup_ms(float *keys_ms, float *sort_ms, float *runs_ms);
+int peakseg_hip_reads_last_dedup_passes(void);
 
 /* Tests: the cluster kernels alone, on caller-given peaks of the members of ONE group, without any
  * solve.  n_peaks[m]: the peaks of member m; peak_start[m] / peak_end[m]: host int32 arrays, sorted

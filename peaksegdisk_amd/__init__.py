@@ -16,12 +16,13 @@ from .api import (PeakSegError, PeakSegFPOP_dir, PeakSegFPOP_df, PeakSegFPOP_fil
                   joint_target_interval_dense, joint_target_interval_reads,
                   learn_joint_penalty_dense, learn_joint_penalty_reads,
                   select_penalty_dense, select_penalty_reads, strand_cross_correlation,
-                  estimate_fragment_length, extend_reads)
+                  estimate_fragment_length, extend_reads, remove_duplicates)
 from ._native import last_fanout  # noqa: F401
 from .grid import ProblemSet, read_labels_bed, features_from_stats  # noqa: F401
 from .joint_target import JointSearch, JointTargetInterval, joint_target_interval  # noqa: F401
 from .heldout import HeldoutSelection  # noqa: F401
 from .strand import FragmentLength  # noqa: F401
+from .dedup import DuplicateRemoval  # noqa: F401
 from .fit import (PenaltyModelFit, fit_penalty_model, learn_penalty_model_dense,  # noqa: F401
                   learn_penalty_model_reads)
 
@@ -39,4 +40,5 @@ __all__ = ["PeakSegFPOP_file", "PeakSegFPOP_dir", "PeakSegFPOP_df", "PeakSegFPOP
            "joint_target_interval_reads", "learn_joint_penalty_dense", "learn_joint_penalty_reads",
            "JointSearch", "JointTargetInterval", "joint_target_interval", "PeakSegError",
            "select_penalty_dense", "select_penalty_reads", "HeldoutSelection",
-           "strand_cross_correlation", "estimate_fragment_length", "extend_reads", "FragmentLength"]
+           "strand_cross_correlation", "estimate_fragment_length", "extend_reads", "FragmentLength",
+           "remove_duplicates", "DuplicateRemoval"]

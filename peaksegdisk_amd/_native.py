@@ -21,6 +21,7 @@ ERROR_FIT_ARGUMENTS = 21
 ERROR_REGION_ARGUMENTS = 22
 ERROR_HELDOUT_ARGUMENTS = 23
 ERROR_STRAND_ARGUMENTS = 24
+ERROR_DEDUP_ARGUMENTS = 25
 
 
 class PsdResult(ctypes.Structure):
@@ -332,6 +333,23 @@ def declare(lib):
     lib.peakseg_hip_xcorr_max_shift.restype = c.c_int
     lib.peakseg_hip_reads_last_xcorr_ms.argtypes = [c.POINTER(c.c_float), c.POINTER(c.c_float)]
     lib.peakseg_hip_reads_last_xcorr_ms.restype = c.c_int
+    lib.peakseg_hip_reads_dedup.argtypes = [
+        c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p), c.POINTER(c.c_void_p), c.c_int, c.c_int, c.c_int,
+        c.POINTER(c.c_void_p), c.c_void_p]
+    lib.peakseg_hip_reads_dedup.restype = c.c_int
+    lib.peakseg_hip_reads_compact.argtypes = [
+        c.c_int, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.POINTER(c.c_void_p), c.c_int] + [c.POINTER(c.c_void_p)] * 5 + [c.c_void_p]
+    lib.peakseg_hip_reads_compact.restype = c.c_int
+    lib.peakseg_hip_dedup_block_rows.argtypes = []
+    lib.peakseg_hip_dedup_block_rows.restype = c.c_int
+    lib.peakseg_hip_dedup_scan_span.argtypes = []
+    lib.peakseg_hip_dedup_scan_span.restype = c.c_int
+    lib.peakseg_hip_reads_last_dedup_ms.argtypes = [c.POINTER(c.c_float)] * 3
+    lib.peakseg_hip_reads_last_dedup_ms.restype = c.c_int
+    lib.peakseg_hip_reads_last_dedup_passes.argtypes = []
+    lib.peakseg_hip_reads_last_dedup_passes.restype = c.c_int
     lib.peakseg_hip_search_place_penalties.argtypes = [
         c.c_double, c.c_double, c.c_double, c.c_int, c.POINTER(c.c_double)]
     lib.peakseg_hip_search_place_penalties.restype = c.c_int
@@ -397,6 +415,9 @@ EXPORTED_SYMBOLS = [
     "peakseg_hip_fold_max_count", "peakseg_hip_fold_units_last_ms",
     "peakseg_hip_reads_strand_xcorr", "peakseg_hip_reads_extend", "peakseg_hip_xcorr_max_shift",
     "peakseg_hip_reads_last_xcorr_ms",
+    "peakseg_hip_reads_dedup", "peakseg_hip_reads_compact", "peakseg_hip_dedup_block_rows",
+    "peakseg_hip_dedup_scan_span", "peakseg_hip_reads_last_dedup_ms",
+    "peakseg_hip_reads_last_dedup_passes",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -656,9 +656,33 @@ def extend_reads(reads, strands, fragment_length, device=0):
     return out[0] if single else out
 
 
+def remove_duplicates(reads, strands=None, keep=1, by=None, compact=True, device=0):
+    """Duplicate removal of aligned reads on the GPU (peakseg_hip_reads_dedup: a stable radix sort of
+    the reads' keys; the definitions are in include/peaksegdisk_hip.h): of every key the first `keep`
+    units survive, in input order.  reads as extend_reads takes them (one contig or a list, numpy
+    arrays or cuda tensors read in place; a row's count is its multiplicity, absent: 1); strands:
+    per contig an int8 array or tensor with +1 or -1 per read, or None.  by: "fragment" -- the key
+    is (chromStart, chromEnd, strand): paired-end fragments, reads used as they are -- or
+    "five_prime" -- (5' base, strand), the rule for single-end reads, which needs strands; None:
+    "five_prime" when strands are given, "fragment" otherwise.  Returns a DuplicateRemoval: .reads,
+    per contig (chromStart, chromEnd, count) -- the tuple itself for a single contig -- in the kind
+    of memory it was given; .strands alike, or None; .summary, a data frame with one row per contig
+    and the int64 columns reads, kept, rows_kept, distinct (distinct / reads is the non-redundant
+    fraction).  compact=True drops the rows that lose every unit; compact=False keeps every row and
+    only changes count, zeros included.  Both forms are what every *_reads entry point,
+    strand_cross_correlation and extend_reads take."""
+    from . import dedup
+    single, contigs, strands = _stranded_contigs(reads, strands)
+    new_reads, new_strands, summary = _strand_call(
+        lambda: dedup.remove(contigs, strands, keep, by, compact, device))
+    return dedup.DuplicateRemoval(new_reads[0] if single else new_reads,
+                                  None if new_strands is None else (new_strands[0] if single else new_strands),
+                                  dedup.summary_frame(summary))
+
+
 def PeakSegFPOP_reads(reads, penalties=None, chrom="chrUnknown", extents=None, bases_counted="each",
                       device=0, stats=False, labels=None, penalty_model=None, strands=None,
-                      fragment_length=None, max_shift=400, min_shift=0):
+                      fragment_length=None, max_shift=400, min_shift=0, max_duplicates=None):
     """PeakSegFPOP_dense with the step in front of it: aligned reads are piled up into coverage,
     run-length encoded and solved on the GPU.  reads: one contig -- (chromStart, chromEnd) or
     (chromStart, chromEnd, count), one entry per read, in any order -- or a list of contigs
@@ -669,7 +693,8 @@ def PeakSegFPOP_reads(reads, penalties=None, chrom="chrUnknown", extents=None, b
     bases_counted: "each" base of a read or only its "end".  Coordinates are genomic: base 0 of a
     contig is its extent's chromStart.  Results, `stats`, `labels` and `penalty_model` as
     PeakSegFPOP_dense.  Single-end reads: strands= and fragment_length= (an integer, one per
-    contig, or "auto" with max_shift and min_shift) as ProblemSet.from_reads takes them."""
+    contig, or "auto" with max_shift and min_shift) as ProblemSet.from_reads takes them.
+    max_duplicates: None, or the units of every key that remove_duplicates leaves, first of all."""
     from .grid import ProblemSet
     single, contigs, strands = _stranded_contigs(reads, strands)
     if (strands is None) != (fragment_length is None):
@@ -682,7 +707,7 @@ def PeakSegFPOP_reads(reads, penalties=None, chrom="chrUnknown", extents=None, b
         pset = ProblemSet.from_reads(contigs, problems, extents=extents,
                                      bases_counted=bases_counted, device=device, strands=strands,
                                      fragment_length=fragment_length, max_shift=max_shift,
-                                     min_shift=min_shift)
+                                     min_shift=min_shift, max_duplicates=max_duplicates)
         return pset, pset.contig_starts
     return _solve_dense_set(make_set, pens, chrom, stats, single, "<aligned reads>", labels,
                             penalty_model)
@@ -1232,21 +1257,26 @@ def targetInterval_reads(reads, labels, width=None, max_rounds=20, extents=None,
 
 def coverage_from_reads(chromStart, chromEnd, count=None, chrom="chrUnknown", extent=None,
                         bases_counted="each", device=0, strands=None, fragment_length=None,
-                        max_shift=400, min_shift=0):
+                        max_shift=400, min_shift=0, max_duplicates=None):
     """The coverage profile of one contig's aligned reads, piled up and run-length encoded on the
     GPU (peakseg_hip_reads_pileup_probe): the data frame chrom, chromStart, chromEnd, count that
     writeBedGraph and PeakSegFPOP_df take -- integer columns, genomic coordinates, runs of zero
     included, so there are no gaps.  The read arrays as ProblemSet.from_reads takes them;
     extent: the (chromStart, chromEnd) to cover, default (min chromStart, max chromEnd).
     Single-end reads: strands= (one int8 array or tensor) and fragment_length= (an integer, or
-    "auto" with max_shift and min_shift) extend the reads first, as ProblemSet.from_reads does."""
+    "auto" with max_shift and min_shift) extend the reads first, as ProblemSet.from_reads does.
+    max_duplicates: None, or the units of every key that remove_duplicates leaves, first of all."""
     import ctypes
+    from .dedup import deduplicated_for
     from .grid import reads_arguments
     from .strand import extended_for
     entry = (chromStart, chromEnd) if count is None else (chromStart, chromEnd, count)
+    strand_list = None if strands is None else [strands]
+    contigs, extents = _strand_call(lambda: deduplicated_for(
+        [entry], strand_list, max_duplicates, None if extent is None else [extent], device, None,
+        "coverage_from_reads"))
     contigs, extents = _strand_call(lambda: extended_for(
-        [entry], None if strands is None else [strands], fragment_length,
-        None if extent is None else [extent], device, None, "coverage_from_reads", max_shift,
+        contigs, strand_list, fragment_length, extents, device, None, "coverage_from_reads", max_shift,
         min_shift))
     args, keep, ext = reads_arguments(contigs, extents, bases_counted, device, "coverage_from_reads")
     lo, hi = ext[0]

@@ -103,6 +103,8 @@
 #include "fold_units.h"
 /* the strand cross-correlation of single-end reads, and their extension to a fragment length */
 #include "strand_xcorr.h"
+/* duplicate removal of reads: a stable radix sort of their keys, the first k units of every key */
+#include "reads_dedup.h"
 /* tests only: every form of the deterministic exp / log, element by element */
 #include "math_forms_probe.h"
 
@@ -150,6 +152,7 @@
 #include "peakseg_joint_labels.h"
 #include "peakseg_heldout.h"
 #include "peakseg_strand.h"
+#include "peakseg_dedup.h"
 
 extern "C" int peakseg_hip_device_count(void) {
   int n = 0;
@@ -597,6 +600,10 @@ extern "C" char *PeakSegFPOP_status_message(int status, const char *bedGraph, co
                 "error code %d: stranded reads that cannot be served (a strand that is neither +1 nor "
                 "-1, a NULL strand array, a max_shift outside 0 .. peakseg_hip_xcorr_max_shift, a "
                 "fragment_length below 1, or an extent with hi <= lo)", status);
+    PSD_MESSAGE(ERROR_DEDUP_ARGUMENTS,
+                "error code %d: a duplicate removal that cannot be served (keep below 1, an unknown "
+                "by, five_prime without strands, 2^31 or more rows in one call, or an output that "
+                "overlaps an input)", status);
     default:
       snprintf(buf, buf_len, "error code %d", status);
       break;

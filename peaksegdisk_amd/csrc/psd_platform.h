@@ -211,6 +211,19 @@ PSD_D void atomic_max_i32(int *p, int v) {
   (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 #endif
+/* the same for a mask of bits (an OR commutes as an add does), and a look at such a word past the
+ * caches of the compute unit */
+#ifdef PSD_EMU
+PSD_D void atomic_or_u32(unsigned *p, unsigned v) { (void)__atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
+PSD_D unsigned agent_load_u32(const unsigned *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+#else
+PSD_D unsigned agent_load_u32(const unsigned *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+PSD_D void atomic_or_u32(unsigned *p, unsigned v) {
+  (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif
 
 /* an add to a word in LDS that other lanes and waves of the workgroup add to as well; nothing is
  * returned (ds_add_u32) */

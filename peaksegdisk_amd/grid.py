@@ -291,7 +291,7 @@ class ProblemSet:
     @classmethod
     def from_reads(cls, reads, problems, extents=None, bases_counted="each", device=0,
                    arena_pieces=0, lib=None, strands=None, fragment_length=None, max_shift=400,
-                   min_shift=0):
+                   min_shift=0, max_duplicates=None):
         """The set of ALIGNED READS: `reads` is a list, one entry per contig, of
         (chromStart, chromEnd) or (chromStart, chromEnd, count) -- 1-d contiguous int32 numpy
         arrays or torch tensors, one entry per read, in any order.  The coverage is piled up and
@@ -307,7 +307,12 @@ class ProblemSet:
         fragment_length (an integer, one per contig, or "auto": the pooled estimate of the strand
         cross-correlation over the shifts min_shift .. max_shift) extend every read from its 5'
         end to the fragment length on the device first (strand.py); the two go together.  Default
-        extents stay those of the reads as given, and the extension is clipped to them."""
+        extents stay those of the reads as given, and the extension is clipped to them.
+        max_duplicates: None, or an integer k: duplicates are removed first (dedup.py) -- at most k
+        units of every key survive, in input order, by 5' end and strand when strands are given,
+        by (chromStart, chromEnd) otherwise -- on the reads as given, before any extension and
+        before "auto" estimates the fragment length."""
+        from .dedup import deduplicated_for
         from .strand import extended_for
         self = cls.__new__(cls)
         self._lib = lib or _native.lib
@@ -315,6 +320,8 @@ class ProblemSet:
         self.dense = True
         self.device = device
         self.problems = [(int(c), float(p)) for c, p in problems]
+        reads, extents = deduplicated_for(reads, strands, max_duplicates, extents, device, self._lib,
+                                          "from_reads")
         reads, extents = extended_for(reads, strands, fragment_length, extents, device, self._lib,
                                       "from_reads", max_shift, min_shift)
         args, keep, ext = reads_arguments(reads, extents, bases_counted, device, "from_reads")

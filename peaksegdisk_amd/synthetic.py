@@ -125,6 +125,32 @@ def shuffled(seed, *arrays):
     return tuple(a[order] for a in arrays)
 
 
+def duplicated_reads(seed, n, bases, share=0.2, read_length=36):
+    """n single-end reads of read_length on [0, bases + read_length) of which floor(share n) are
+    duplicates: (chromStart, chromEnd) int32, the strand int8 and the number of duplicates.  uK is
+    uniform01(seed, K, .).  The m = n - duplicates originals have distinct starts
+    i step + floor(u21 step), step = bases // m, and the strand +1 iff u22 < 0.5, so their keys are
+    distinct by fragment and by 5' end alike; duplicate j is a copy of original floor(u23 m), strand
+    included; all of them in the order of u24 (stable).  At keep = 1 a removal leaves exactly the m
+    originals' units: distinct = kept = m of n reads."""
+    n = int(n)
+    dup = int(share * n)
+    m = n - dup
+    step = int(bases) // max(m, 1)
+    if m < 1 or step < 1:
+        raise ValueError("duplicated_reads: %d originals do not fit %d bases" % (m, bases))
+    start = np.arange(m, dtype=np.int64) * step + np.floor(uniform01(seed, 21, m) * step).astype(np.int64)
+    strand = np.where(uniform01(seed, 22, m) < 0.5, 1, -1).astype(np.int8)
+    source = np.minimum(np.floor(uniform01(seed, 23, dup) * m).astype(np.int64), m - 1)
+    start = np.concatenate([start, start[source]])
+    strand = np.concatenate([strand, strand[source]])
+    order = np.argsort(uniform01(seed, 24, n), kind="stable")
+    start, strand = start[order], strand[order]
+    if n and start.max() + read_length >= 2 ** 31:
+        raise ValueError("synthetic reads exceed int32 coordinates")
+    return start.astype(np.int32), (start + read_length).astype(np.int32), strand, dup
+
+
 def increasing_coverage(n_bins):
     """Worst case of vignettes/Worst_case.Rmd:26-28: count = 1..N, width 1."""
     n_bins = int(n_bins)
